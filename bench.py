@@ -2,14 +2,20 @@
 """Benchmark: batched CvRDT lub (replica-merges/s) on MI355X — BASELINE.json config 2 (`value`) and
 config 5 (the `c5` block of the same line).
 
+A plain run (`--gpus N --steps K --warmup W`) generates the headline workload's replicas, warms up,
+times K steps, writes the last step's result with --dump-outputs DIR, and prints the JSON line with
+the headline figure (`value`, `ms_per_step`, `step_ms`, `roofline` from the timed steps' own
+timers).  Everything else described below — the parity checks, the `c5` / `c3` / `c4` blocks, the
+CPU baselines — runs with --full only (a failed check there exits 3).
+
 --workload c2 (default): one step = the two lubs of config 2 over HBM-resident synthetic replicas:
     GCounter  lub_many of 1,048,576 replicas x 256 actors (u64)       2 GiB read
     PNCounter lub_many of 1,048,576 replicas x (2 x 256) actors (u64)  4 GiB read
-= 2,097,152 replica-merges per rank per step.  The same line then carries a `c5` block: one step =
+= 2,097,152 replica-merges per rank per step.  With --full the line then carries a `c5` block: one step =
 one GPU's shard of config 5, VClock lub_many of 1,048,576 replicas x 1,024 actors (8 GiB read; at
 --gpus 8 the global input is config 5's 8M replicas and the exchange its RCCL max all-reduce).
 --workload c5: config 5 as the headline instead (no second block).
-At N = 1 the line also carries `c3` and `c4` blocks (--no-c3 / --no-c4 drop them): BASELINE config 3,
+At N = 1 a --full line also carries `c3` and `c4` blocks (--no-c3 / --no-c4 drop them): BASELINE config 3,
 Orswot<u64, u32> lub_many of 65,536 replicas x 4,096 members x 64 actors with deferred removes (128 GiB
 of entries), and config 4, Map<u32, MVReg<u64>> lub_many of 16,384 replicas x 1,024 keys x 32 actors,
 V = 2 (12.25 GiB), both generated in HBM; one step = one whole lub_many (every kernel of it), the
@@ -35,7 +41,11 @@ The JSON line also carries
                 stream vs the algorithmic bytes per launch, against 8 TB/s
   cpu_baseline  the oracle's restated reference fold (VClock::merge over ordered maps) on a
                 bounded sample of the same workload, split over the host's threads (up to 16),
-                plus the one-thread figure (rank 0 at N=1 only).
+                plus the one-thread figure (--full, rank 0 at N=1 only).
+
+--dump-outputs DIR: after the timed steps rank 0 writes the headline workload's result of the last
+timed step (see dump_outputs) as DIR/<name>.npy.  The input is a pure function of the arguments
+(counter-based generator, fixed seeds), so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -61,6 +71,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps also run everything else the line can carry: the parity "
+                         "checks, the `c5` / `c3` / `c4` blocks and the CPU baselines (a plain run only sets up, warms "
+                         "up, times --steps steps of --workload and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of the headline workload returned as DIR/<name>.npy "
+                         "(float64; see dump_outputs)")
     ap.add_argument("--workload", choices=("c2", "c5"), default=os.environ.get("CRDT_BENCH_WORKLOAD", "c2"),
                     help="c2: GCounter+PNCounter 1M x 256 (BASELINE config 2) + a config-5 block; c5: VClock "
                          "1M x 1024 per GPU (one shard of config 5) only")
@@ -98,7 +115,10 @@ def parse():
                     help="replicas of the c4 multi-core CPU baseline (key ranges per thread)")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"),
                     help="PMC-derived HBM bytes per launch (written by profiles/collect.sh)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 KERNEL_SOURCES = {"c2": "lattice.hip", "c5": "lattice.hip", "c3": "orswot.hip", "c4": "map.hip"}
@@ -331,8 +351,23 @@ def oracle_parity_counters(args, torch, lubs, outs, A):
             "seconds": time.time() - t0}
 
 
-def run_workload(args, env, workload):
-    """Generate the rank's shard in HBM, warm up, time args.steps steps; return the measured block."""
+def dump_outputs(dump_dir, lubs, outs):
+    """--dump-outputs: the lub of every type of the step as the caller receives it after the last timed
+    step (A u64 counters; 2A for PNCounter), as float64 .npy files.  A u64 does not fit a float64, so
+    each lub is written three times: <kind>.npy (the value rounded to float64) and the exact halves
+    <kind>_hi32.npy / <kind>_lo32.npy (value = hi32 * 2**32 + lo32)."""
+    import numpy as np
+    os.makedirs(dump_dir, exist_ok=True)
+    for (kind, _, _), o in zip(lubs, outs):
+        v = o.cpu().numpy().view(np.uint64)
+        np.save(os.path.join(dump_dir, f"{kind}.npy"), v.astype(np.float64))
+        np.save(os.path.join(dump_dir, f"{kind}_hi32.npy"), (v >> np.uint64(32)).astype(np.float64))
+        np.save(os.path.join(dump_dir, f"{kind}_lo32.npy"), (v & np.uint64(0xFFFFFFFF)).astype(np.float64))
+
+
+def run_workload(args, env, workload, dump_dir=None):
+    """Generate the rank's shard in HBM, warm up, time args.steps steps; return the measured block.
+    The parity checks run with --full only."""
     torch, cg, cdist = env.torch, env.cg, env.cdist
     ctx, world, rank = env.ctx, env.world, env.rank
     R = args.replicas
@@ -397,18 +432,24 @@ def run_workload(args, env, workload):
     elapsed = env.max_over_ranks([elapsed])[0]
     xch_ms, agr_ms = env.max_over_ranks([xch_ms, agr_ms])
 
-    # Parity (outside the timed region): unsigned max with torch ops; for N > 1 the exchanged
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, lubs, outs)
+
+    # Parity (--full; outside the timed region): unsigned max with torch ops; for N > 1 the exchanged
     # result must equal the max over every rank's torch reference (torch.distributed's own exchange)
-    sign = torch.tensor(-(2**63), dtype=torch.int64, device="cuda")
-    refs = [(x ^ sign).amax(0) ^ sign for _, x, _ in lubs]
-    got, ref = torch.cat(outs), torch.cat(refs)
-    if world > 1:
-        cdist.allreduce_umax_(ref)
-    ok = env.max_over_ranks([0.0 if bool(torch.equal(got, ref)) else 1.0])[0] == 0.0
+    ok, torch_par = True, "unchecked (--full checks it)"
+    if args.full:
+        sign = torch.tensor(-(2**63), dtype=torch.int64, device="cuda")
+        refs = [(x ^ sign).amax(0) ^ sign for _, x, _ in lubs]
+        got, ref = torch.cat(outs), torch.cat(refs)
+        if world > 1:
+            cdist.allreduce_umax_(ref)
+        ok = env.max_over_ranks([0.0 if bool(torch.equal(got, ref)) else 1.0])[0] == 0.0
+        torch_par = "ok" if ok else "MISMATCH"
     # and (N = 1, rank 0, with the CPU leg) the oracle's restated fold on a sample of actors over
     # every replica row: the CPU check the c3 / c4 blocks already carry
-    oracle_par = {"result": "unchecked (the oracle leg runs at N = 1 without --no-cpu-baseline)"}
-    if world == 1 and not args.no_cpu_baseline:
+    oracle_par = {"result": "unchecked (the oracle leg runs with --full at N = 1 without --no-cpu-baseline)"}
+    if args.full and world == 1 and not args.no_cpu_baseline:
         oracle_par = oracle_parity_counters(args, torch, lubs, outs, A)
 
     merges_per_step = len(lubs) * R * world
@@ -464,8 +505,9 @@ def run_workload(args, env, workload):
             "launches": launches,
             "algorithmic_bytes_per_launch": avg_launch_bytes,
         },
-        "parity": "ok" if ok and oracle_par["result"] != "MISMATCH" else "MISMATCH",
-        "parity_detail": {"torch_umax": "ok" if ok else "MISMATCH", "oracle": oracle_par},
+        "parity": (torch_par if not args.full else
+                   "ok" if ok and oracle_par["result"] != "MISMATCH" else "MISMATCH"),
+        "parity_detail": {"torch_umax": torch_par, "oracle": oracle_par},
     }
     if env.cabi:  # where a scaling loss goes: the exchange collectives and the per-call agreement
         block["exchange"] = {
@@ -723,18 +765,18 @@ def main():
               "size than requested", file=sys.stderr)
         sys.exit(2)
     env = Env(args)
-    head, A = run_workload(args, env, args.workload)
+    head, A = run_workload(args, env, args.workload, dump_dir=args.dump_outputs)
     c5 = None
-    if args.workload == "c2" and args.c5:
+    if args.full and args.workload == "c2" and args.c5:
         c5, _ = run_workload(args, env, "c5")
     causal = {}
     for blk in ("c3", "c4"):
         on = getattr(args, blk)
         if on is None:
             on = env.world == 1
-        if on:
+        if on and args.full:
             causal[blk] = run_causal(args, env, blk)
-    ok = (head["parity"] == "ok" and (c5 is None or c5["parity"] == "ok")
+    ok = (head["parity"] != "MISMATCH" and (c5 is None or c5["parity"] == "ok")
           and all(b["parity"]["result"] != "MISMATCH" for b in causal.values()))
     if env.rank == 0:
         out = {
@@ -744,6 +786,7 @@ def main():
             "n_gpus": env.world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": head["ms_per_step"],
             "step_ms": head["step_ms"],
             "higher_is_better": True,
@@ -764,7 +807,7 @@ def main():
         if c5 is not None:
             out["c5"] = dict(c5, metric=METRIC + " — BASELINE config 5 (VClock 1,024 actors; 8M replicas at 8 GPUs)")
         out.update(causal)
-        if env.world == 1 and not args.no_cpu_baseline:
+        if args.full and env.world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, args.workload, A)
         print(json.dumps(out), flush=True)
     if env.world > 1:

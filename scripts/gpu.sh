@@ -27,8 +27,8 @@ case "$mode" in
     rc=$?; echo "pytest rc=$rc"; tail -n 5 gpurun_out/pytest_gpu_$tag.log; [ $rc -ne 0 ] && exit $rc
     timeout -k 10 180 python -u -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke_$tag.log 2>&1 || exit $?
     tail -n 1 gpurun_out/smoke_$tag.log
-    timeout -k 10 300 python -u bench.py > gpurun_out/bench_$tag.log 2>&1 || exit $?
-    grep '^{' gpurun_out/bench_$tag.log | cut -c1-400
+    timeout -k 10 600 python -u bench.py --full > "$TMPDIR/bench_$tag.log" 2>&1 || { rc=$?; tail -n 20 "$TMPDIR/bench_$tag.log"; exit $rc; }
+    grep '^{' "$TMPDIR/bench_$tag.log" | cut -c1-400
     bash profiles/collect.sh "$tag" ;;
   run)
     tag=$1; shift
