@@ -648,9 +648,17 @@ int crdt_lwwreg_lub_many_sharded(crdt_ctx *ctx, const uint64_t *marker, const ui
  * report it).  The state holds VO = 2*pow2(V') values, V' the
  * smallest power of two with V' >= V and 2V' >= min(8, max(Vout, Vstate)); VO <= 8.
  * Deferred output as for Orswot (def_keep / def_keys over keys).
- * Limits: A <= 1024, V <= 16, Vout <= 64; the fold state holds up to 16 values per key (bit 2 of
- * flags when a key needs more).  A > 256 or V > 8 runs the workgroup-per-key fold (csrc/map_wide.hip:
- * the same exact left fold, no speculative scan — a correctness path, not a tuned one). */
+ * Limits: A <= 1024, V <= 16, Vout <= 64.  With Vstate <= 16 the fold state holds up to 16 values per
+ * key (bit 2 of flags when a key needs more).  17 <= Vstate <= 64 asks for the deep pass
+ * (csrc/map_deep.hip): the fold runs as with Vstate = 0, the keys whose state overflows are marked
+ * instead of reported, and a second kernel on the same stream folds each marked key again, exactly
+ * and in replica order, with up to Vstate values held in LDS; bit 2 then means that a key needed more
+ * than Vstate values at some step, bit 0 as before.  The deep pass needs about Vstate * A * 8 + 14 KiB
+ * of LDS per key: past 160 KiB (Vstate = 64: A > 256) the call returns CRDT_EUNSUPPORTED before
+ * anything is launched, as it does for Vstate > 64.  The sharded and CRDT_MEM_HOST entry points have
+ * no deep pass: they treat Vstate > 16 as 16.  A > 256 or V > 8 runs the workgroup-per-key fold
+ * (csrc/map_wide.hip: the same exact left fold, no speculative scan — a correctness path, not a
+ * tuned one). */
 typedef struct crdt_map_batch {
   size_t G, R, K, A, V;
   const uint64_t *clock;
@@ -669,7 +677,8 @@ typedef struct crdt_map_batch {
 
 typedef struct crdt_map_out {
   size_t Vout;
-  size_t Vstate; /* value capacity hint for the fold state (0 = from Vout and V) */
+  size_t Vstate; /* <= 16: value capacity hint for the fold state (0 = from Vout and V);
+                    17..64: the deep pass with that many values per key (see Limits) */
   uint64_t *clock; /* [G][A]          */
   uint64_t *ec;    /* [G][K][A]       */
   uint64_t *vclk;  /* [G][K][Vout][A] */
@@ -988,7 +997,8 @@ int crdt_map_nested_merge_batch(crdt_ctx *ctx, const crdt_map_nested_states *sel
  *                (g, r) at vclk + g*vclk_gstride + r*vclk_rstride (vval likewise).  out: Vout slots
  *                per group (packed [G][Vout][A] / [G][Vout]), nval[g] (may be NULL), flags[g]: bit 0
  *                = more than Vout values (slots incomplete: retry with a larger Vout), bit 2 = the
- *                fold state overflowed (retry with Vstate = 16; past 16 values it is reported).
+ *                fold state overflowed (retry with Vstate = 16; past 16 values it is reported, or
+ *                folded exactly by the deep pass: Vstate = 17..64, see Limits).
  *   merge_batch: self[i].merge(other[i]), in place in self's V slots (own kept values, then other's
  *                added ones); status[i] bit 4 = more than self's V values (register incomplete).
  *   apply_batch: register i applies ops [op_off[i], op_off[i+1]) in order, Op::Put { clock:
@@ -996,7 +1006,12 @@ int crdt_map_nested_merge_batch(crdt_ctx *ctx, const crdt_map_nested_states *sel
  *                of range (skipped), bit 3 = op_off invalid (register untouched), bit 4 = more than
  *                V values.
  * Limits: A <= 1024, 1 <= V <= 16 (lub_many: Vout <= 16); A > 256 or V > 8 run one workgroup of
- * ceil(A / 64) waves per register. */
+ * ceil(A / 64) waves per register.  lub_many with 17 <= Vstate <= 64 adds a deep pass: Vout may go up
+ * to 64, the registers whose 16-value state overflows are marked instead of reported and folded
+ * again, in replica order, with up to Vstate values held in LDS (bit 2 = more than Vstate values at
+ * some step).  It needs about Vstate * A * 8 bytes of LDS per register; past 160 KiB, or with
+ * Vstate > 64, the call returns CRDT_EUNSUPPORTED before anything is launched.  merge_batch and
+ * apply_batch keep their limits. */
 typedef struct crdt_mvreg_states {
   size_t N, A, V;
   uint64_t *vclk;
@@ -1015,7 +1030,8 @@ typedef struct crdt_mvreg_batch {
 
 typedef struct crdt_mvreg_out {
   size_t Vout;
-  size_t Vstate;   /* value capacity hint for the fold state (0 = from Vout and V) */
+  size_t Vstate;   /* <= 16: value capacity hint for the fold state (0 = from Vout and V);
+                      17..64: the deep pass with that many values (see Limits) */
   uint64_t *vclk;  /* [G][Vout][A] */
   uint64_t *vval;  /* [G][Vout]    */
   uint32_t *nval;  /* [G] or NULL  */

@@ -52,7 +52,11 @@ def lub_many(clock: torch.Tensor, ec: torch.Tensor, vclk: torch.Tensor, vval: to
              def_clock: Optional[torch.Tensor] = None, def_keys: Optional[torch.Tensor] = None,
              vout: int = 4, ctx: Optional[Context] = None, check: bool = True,
              vstate: int = 0, _key_shard: Optional[tuple] = None) -> MapLub:
-    """`_key_shard=(k0, K_total)`: this rank's keys [k0, k0 + K) of a key-sharded fold through the
+    """`vstate`: the fold state's value slots per key.  Up to 16 it sizes the fold kernel's state (a
+    smaller one is retried larger on overflow); 17..64 asks for the deep pass, which folds the keys
+    that overflow 16 values again, exactly, with `vstate` slots (MapCapacityError past that).
+
+    `_key_shard=(k0, K_total)`: this rank's keys [k0, k0 + K) of a key-sharded fold through the
     C ABI's communicator (crdt_map_lub_many_sharded; use crdts_gpu.shard.map_lub_many_sharded):
     def_keys / the returned def_keys are then over all K_total keys."""
     ctx = ctx or Context.default(clock.device.index)
@@ -154,9 +158,13 @@ def lub_many(clock: torch.Tensor, ec: torch.Tensor, vclk: torch.Tensor, vval: to
         if f & 4 and vstate < 16 and _key_shard is None:
             return lub_many(clock, ec, vclk, vval, def_off, def_row, def_clock, def_keys, vout, ctx,
                             check, vstate=8 if vstate < 8 else 16, _key_shard=_key_shard)
+        if f & 4 and vstate > 16 and _key_shard is None:  # the deep pass ran out of its slots too
+            raise MapCapacityError(f"map.lub_many: a key held more than vstate={vstate} MVReg values "
+                                   "during the fold; results incomplete (vstate goes up to 64)")
         if f & 4 and (vstate >= 16 or _key_shard is not None):
             raise MapCapacityError("map.lub_many: a key held more than 16 MVReg values during the "
-                                   "fold (the kernel's state capacity); results incomplete")
+                                   "fold (the first pass's state capacity); results incomplete. "
+                                   "Pass vstate=17..64 for the deep pass (device memory, unsharded)")
         if f & 1:
             raise MapCapacityError(f"map.lub_many: a key folds to more than vout={vout} values; "
                                    "retry with a larger vout")

@@ -45,7 +45,9 @@ def _check_regs(ctx, vclk, vval, what, lead):
 def lub_many(vclk: torch.Tensor, vval: torch.Tensor, vout: int = 4, ctx: Optional[Context] = None,
              check: bool = True, vstate: int = 0) -> MVRegLub:
     """Left fold of each group's replicas from MVReg::new().  A group needing more than `vout`
-    values raises MVRegCapacityError (check=True); a fold state overflow reruns with 16 slots."""
+    values raises MVRegCapacityError (check=True); a fold state overflow reruns with 16 slots.
+    `vstate` = 17..64 asks for the deep pass (registers that overflow 16 values are folded again with
+    `vstate` slots); `vout` may then go up to 64 instead of 16."""
     ctx = ctx or Context.default(vclk.device.index)
     squeeze = vclk.dim() == 3
     vc = vclk.unsqueeze(0) if squeeze else vclk
@@ -65,8 +67,12 @@ def lub_many(vclk: torch.Tensor, vval: torch.Tensor, vout: int = 4, ctx: Optiona
         f = int(np.bitwise_or.reduce(flags.cpu().numpy())) if G else 0
         if f & 4 and vstate < 16:
             return lub_many(vclk, vval, vout, ctx, check, vstate=16)
+        if f & 4 and vstate > 16:  # the deep pass ran out of its slots too
+            raise MVRegCapacityError(f"mvreg.lub_many: a register held more than vstate={vstate} values "
+                                     "during the fold (vstate goes up to 64)")
         if f & 4:
-            raise MVRegCapacityError("mvreg.lub_many: a register held more than 16 values during the fold")
+            raise MVRegCapacityError("mvreg.lub_many: a register held more than 16 values during the fold "
+                                     "(pass vstate=17..64 for the deep pass)")
         if f & 1:
             raise MVRegCapacityError(f"mvreg.lub_many: a register folds to more than vout={vout} values")
     if squeeze:

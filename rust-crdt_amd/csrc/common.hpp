@@ -308,7 +308,26 @@ int map_orswot_lub_many_host(crdt_ctx *ctx, const crdt_map_orswot_batch *in, crd
 int map_nested_lub_many_host(crdt_ctx *ctx, const crdt_map_nested_batch *in, crdt_map_nested_out *out);
 // The workgroup-per-key Map fold for A > 256 or V > 8 (map_wide.hip): def_off_dev = the device copy
 // of the deferred offsets (or NULL); outputs and flags as crdt_map_lub_many (flags zeroed by the caller).
-int map_lub_wide(crdt_ctx *ctx, const crdt_map_batch *in, const size_t *def_off_dev, crdt_map_out *out);
+// deep: a deep pass follows (out->nval is then required): a key whose 16-value state overflowed gets
+// nval = kMapDeepMark instead of flags bits 0 / 2.
+int map_lub_wide(crdt_ctx *ctx, const crdt_map_batch *in, const size_t *def_off_dev, crdt_map_out *out, bool deep);
+// The deep pass of crdt_map_lub_many (map_deep.hip): the keys the first pass marked in out->nval
+// (required) folded again with out->Vstate (17..64) value slots in LDS.  map_deep_lds: the LDS bytes
+// one workgroup needs.
+size_t map_deep_lds(size_t Vstate, size_t A);
+int map_lub_deep(crdt_ctx *ctx, const crdt_map_batch *in, const size_t *def_off_dev, crdt_map_out *out);
+constexpr unsigned kMapDeepMark = 0x80000000u;  // nval of a key left to the deep pass (a count is <= 64)
+// map_fold_kernel learns of the deep pass from bit 0 of its (4-byte aligned) nval pointer
+constexpr uintptr_t kMapDeepTag = 1;
+inline unsigned *map_deep_tag(uint32_t *nval) {
+  return reinterpret_cast<unsigned *>(reinterpret_cast<uintptr_t>(nval) | kMapDeepTag);
+}
+__host__ __device__ inline bool map_deep_tagged(const unsigned *nval) {
+  return (reinterpret_cast<uintptr_t>(nval) & kMapDeepTag) != 0;
+}
+__host__ __device__ inline unsigned *map_deep_untag(unsigned *nval) {
+  return reinterpret_cast<unsigned *>(reinterpret_cast<uintptr_t>(nval) & ~kMapDeepTag);
+}
 int map_merge_batch_host(crdt_ctx *ctx, const crdt_map_states *self, const crdt_map_deferred *self_def,
                          const crdt_map_states *other, const crdt_map_deferred *other_def, uint32_t *status);
 void free_stage(crdt_ctx *ctx);

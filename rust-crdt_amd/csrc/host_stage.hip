@@ -684,7 +684,8 @@ static int map_lub_host_body(crdt_ctx *ctx, const crdt_map_batch *in, crdt_map_o
   b.vclk = vc, b.vclk_rstride = K * V * A, b.vclk_gstride = R * K * V * A;
   b.vval = vv, b.vval_rstride = K * V, b.vval_gstride = R * K * V;
   b.def_row = D ? drow : nullptr, b.def_clock = D ? dc : nullptr, b.def_keys = D ? dk : nullptr;
-  crdt_map_out o{Vo, out->Vstate, oc, oec, ovc, ovv, onv, ofl, okp, odk};
+  // (the host-memory fold keeps the 16-value state: Vstate > 16, the deep pass, is device-memory only)
+  crdt_map_out o{Vo, std::min<size_t>(out->Vstate, 16), oc, oec, ovc, ovv, onv, ofl, okp, odk};
   {
     DeviceModeScope dev(ctx);
     if (int rc = crdt_map_lub_many(ctx, &b, &o)) return rc;
@@ -864,7 +865,7 @@ static int map_lub_host_stream(crdt_ctx *ctx, const crdt_map_batch *in, crdt_map
       cb.def_clock = p_pack + rw;
       cb.def_keys = p_pack + rw + np * A;
     }
-    size_t vstate = out->Vstate;
+    size_t vstate = std::min<size_t>(out->Vstate, 16);  // (no deep pass here, as above)
     for (;;) {  // a fold state that ran out of value slots reruns this chunk (slot 0 still holds acc_k)
       crdt_map_out co{Vi, vstate, a_c, a_ec, a_vc, a_vv, d_nval, d_flags, np ? p_keep : nullptr,
                       np ? p_keys_out : nullptr};

@@ -50,6 +50,10 @@ struct MapPlan {
   const u64 *def_keys;
   unsigned long long G, R, K, A, V, Kw, Vout;
   u64 *o_clock, *o_ec, *o_vclk, *o_vval;
+  // o_nval with bit 0 of the POINTER set (kMapDeepTag, common.hpp): a deep pass follows (map_deep.hip), and a
+  // key whose state overflowed gets nval = kMapDeepMark instead of its group's flags bits 0 / 2.  (A tag on
+  // a pointer the epilogue holds anyway: a plan field of its own stays live through the whole fold and
+  // moved the register allocation of the fast paths, +0.18% at config 4, profiles/map_deep_ab.log.)
   unsigned *o_nval;
   unsigned *o_flags;  // per group: bit0 > Vout values, bit1 bad def_row, bit2 state capacity,
                       // bit3 SH ring arrival wait past its bound (internal fault)
@@ -2393,7 +2397,9 @@ __global__ __launch_bounds__(SH ? 256 : (ST ? 128 : 64), ST ? 2 : 1) void map_fo
         if (rank[q] == (int)o) v = mv.v[q];
       p.o_vval[gk * p.Vout + o] = v;
     }
-    if (p.o_nval) p.o_nval[gk] = present ? (unsigned)nv : 0u;
+    unsigned nvw = present ? (unsigned)nv : 0u;
+    if (map_deep_tagged(p.o_nval) && (ovf & 4)) nvw = kMapDeepMark, ovf &= ~5;  // the deep pass redoes this key
+    if (unsigned *nvp = map_deep_untag(p.o_nval)) nvp[gk] = nvw;
     const unsigned f = (unsigned)ovf | (bad ? 2u : 0u) | (sh_late ? 8u : 0u);
     if (f) atomicOr(p.o_flags + g, f);
   }
@@ -2529,6 +2535,12 @@ static int map_lub_impl(crdt_ctx *ctx, const crdt_map_batch *in, const u64 *doff
   // past the fast kernels' register shapes: the workgroup-per-key fold (map_wide.hip)
   const bool wide = A > 256 || V > 8;
   if (Vout > 64) return fail(ctx, CRDT_EUNSUPPORTED, "map_lub_many: Vout = %zu > 64", Vout);
+  // 17 <= Vstate <= 64: the deep pass (map_deep.hip) redoes the keys whose 16-value state overflows
+  const bool deep = out->Vstate > 16;
+  if (out->Vstate > 64) return fail(ctx, CRDT_EUNSUPPORTED, "map_lub_many: Vstate = %zu > 64", out->Vstate);
+  if (deep && map_deep_lds(out->Vstate, A) > 160 * 1024)
+    return fail(ctx, CRDT_EUNSUPPORTED, "map_lub_many: Vstate = %zu values of A = %zu actors need %zu bytes of LDS (> 160 KiB)",
+                out->Vstate, A, map_deep_lds(out->Vstate, A));
   if (G * K > 0x7fffffffULL) return fail(ctx, CRDT_EUNSUPPORTED, "map_lub_many: G*K too large");
   if (R > 0xfffffffeULL) return fail(ctx, CRDT_EUNSUPPORTED, "map_lub_many: R too large");
   const size_t D = doff ? Ddev : (in->def_off && G > 0) ? in->def_off[G] - in->def_off[0] : 0;
@@ -2538,7 +2550,8 @@ static int map_lub_impl(crdt_ctx *ctx, const crdt_map_batch *in, const u64 *doff
   if (D > 0xffffffffULL) return fail(ctx, CRDT_EUNSUPPORTED, "map_lub_many: too many deferred");
   CRDT_HIP(ctx, hipSetDevice(ctx->device));
   const size_t Kw = (K + 63) / 64;
-  const size_t want = out->Vstate > Vout ? out->Vstate : Vout;
+  // (with a deep pass the first pass's kernel and state are chosen from Vout and V alone)
+  const size_t want = !deep && out->Vstate > Vout ? out->Vstate : Vout;
 
   MapPlan p{};
   p.clock = (const u64 *)in->clock;
@@ -2583,13 +2596,20 @@ static int map_lub_impl(crdt_ctx *ctx, const crdt_map_batch *in, const u64 *doff
   // the RS path: register-staged whole-chunk skip, LDS only for chunks it cannot skip
   const bool rs = glds && ctx->tune.map_rs && A <= 32;
   const unsigned gC = (!rs && ctx->tune.map_chunk == 8 && ctx->tune.map_ring == 4) ? 8 : 16;  // launch_map_glds
-  // scratch: [def_off copy | chunk clock maxima]
+  // scratch: [def_off copy | chunk clock maxima | an nval array for the deep pass when the caller has none]
   const size_t off_b = D > 0 || doff ? ((G + 1) * sizeof(size_t) + 255) / 256 * 256 : 0;
   if (glds) p.nch = (R + gC - 1) / gC;
   p.st = rs && ctx->tune.map_st && A == 32 && V == 2 && !(ctx->tune.map_sh && K % 4 == 0);
   const size_t cm_b = glds ? G * p.nch * A * sizeof(u64) : 0;
-  if (off_b + cm_b > 0)
-    if (int rc = ensure_scratch(ctx, off_b + cm_b)) return rc;
+  const size_t cm_pad = (cm_b + 15) / 16 * 16, nv_b = deep && !out->nval ? G * K * sizeof(unsigned) : 0;
+  if (off_b + cm_pad + nv_b > 0)
+    if (int rc = ensure_scratch(ctx, off_b + cm_pad + nv_b)) return rc;
+  // the first pass marks the overflowed keys in nval (every (g, k) is written by it: nothing to clear)
+  crdt_map_out dout = *out;
+  if (deep) {
+    if (!dout.nval) dout.nval = reinterpret_cast<uint32_t *>(static_cast<char *>(ctx->scratch) + off_b + cm_pad);
+    p.o_nval = map_deep_tag(dout.nval);
+  }
   if (doff && D == 0)  // no pool: only the offsets' check (every entry must be 0)
     if (int rc = stage_def_off_dev(ctx, doff, (size_t *)ctx->scratch, G, 0, nullptr, out->flags)) return rc;
   if (D > 0) {
@@ -2608,7 +2628,7 @@ static int map_lub_impl(crdt_ctx *ctx, const crdt_map_batch *in, const u64 *doff
   const unsigned long long blocks = G * K;
   hipError_t he;
   if (wide) {
-    if (int rc = map_lub_wide(ctx, in, p.def_off, out)) return rc;
+    if (int rc = map_lub_wide(ctx, in, p.def_off, &dout, deep)) return rc;
     he = hipSuccess;
   } else {
   if (glds) {
@@ -2638,6 +2658,9 @@ static int map_lub_impl(crdt_ctx *ctx, const crdt_map_batch *in, const u64 *doff
   timing_end(ctx);
   }
   if (he != hipSuccess) return hip_fail(ctx, he, "map_fold_kernel launch");
+  // the marked keys again, exactly, with Vstate slots (same stream: no host synchronisation between)
+  if (deep)
+    if (int rc = map_lub_deep(ctx, in, p.def_off, &dout)) return rc;
 
   if (D == 0) return CRDT_OK;
   DefPlan q{};

@@ -21,6 +21,7 @@
 // :336-345).
 #include <algorithm>
 
+#include "block_vote.hpp"
 #include "common.hpp"
 
 namespace crdt {
@@ -46,49 +47,8 @@ struct MapWidePlan {
   unsigned long long G, R, K, A, V, Kw, Vout;
   u64 *o_clock, *o_ec, *o_vclk, *o_vval;
   unsigned *o_flags, *o_nval;
+  bool deep;  // a deep pass follows (map_deep.hip): an overflowed key gets nval = kMapDeepMark, not flags bits 0 / 2
 };
-
-// Block-wide AND / OR of NA + NO 64-bit words: wave shuffles, then one word set per wave in LDS.
-// Every thread gets the result.  `red` holds 4 waves * (NA + NO) words.
-template <int NA, int NO>
-__device__ __forceinline__ void wide_vote(u64 (&a)[NA > 0 ? NA : 1], u64 (&o)[NO > 0 ? NO : 1], u64 *red) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-    for (int w = 0; w < NA; ++w) a[w] &= __shfl_xor(a[w], off, 64);
-#pragma unroll
-    for (int w = 0; w < NO; ++w) o[w] |= __shfl_xor(o[w], off, 64);
-  }
-  const int nw = blockDim.x / 64, wv = threadIdx.x / 64;
-  if (nw == 1) return;
-  constexpr int NWD = NA + NO;
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int w = 0; w < NA; ++w) red[wv * NWD + w] = a[w];
-#pragma unroll
-    for (int w = 0; w < NO; ++w) red[wv * NWD + NA + w] = o[w];
-  }
-  __syncthreads();
-  for (int x = 0; x < nw; ++x) {
-#pragma unroll
-    for (int w = 0; w < NA; ++w) a[w] &= red[x * NWD + w];
-#pragma unroll
-    for (int w = 0; w < NO; ++w) o[w] |= red[x * NWD + NA + w];
-  }
-  __syncthreads();  // red may be reused by the next round
-}
-
-// single-flag forms
-__device__ __forceinline__ bool wide_all(bool t, u64 *red) {
-  u64 a[1] = {t ? 1ull : 0ull}, o[1] = {0};
-  wide_vote<1, 0>(a, o, red);
-  return a[0] != 0;
-}
-__device__ __forceinline__ bool wide_any(bool t, u64 *red) {
-  u64 a[1] = {~0ull}, o[1] = {t ? 1ull : 0ull};
-  wide_vote<0, 1>(a, o, red);
-  return o[0] != 0;
-}
 
 template <int VOS>
 struct WideMV {
@@ -510,7 +470,9 @@ __global__ __launch_bounds__(256) void map_fold_wide_kernel(MapWidePlan p) {
         if (rank[q] == (int)o) v = mv.v[q];
       p.o_vval[gk * p.Vout + o] = v;
     }
-    if (p.o_nval) p.o_nval[gk] = present ? (unsigned)nv : 0u;
+    unsigned nvw = present ? (unsigned)nv : 0u;
+    if (p.deep && (ovf & 4)) nvw = kMapDeepMark, ovf &= ~5;  // the deep pass redoes this key
+    if (p.o_nval) p.o_nval[gk] = nvw;
     const unsigned f = (unsigned)ovf | (bad ? 2u : 0u);
     if (f) atomicOr(p.o_flags + g, f);
   }
@@ -518,7 +480,7 @@ __global__ __launch_bounds__(256) void map_fold_wide_kernel(MapWidePlan p) {
 
 // The wide fold of crdt_map_lub_many (map.hip dispatches here when A > 256 or V > 8): the state
 // holds VOS = 4, 8 or 16 values (the caller's Vstate / Vout, retried larger on flags bit 2).
-int map_lub_wide(crdt_ctx *ctx, const crdt_map_batch *in, const size_t *def_off_dev, crdt_map_out *out) {
+int map_lub_wide(crdt_ctx *ctx, const crdt_map_batch *in, const size_t *def_off_dev, crdt_map_out *out, bool deep) {
   const size_t A = in->A, V = in->V;
   if (A > 1024) return fail(ctx, CRDT_EUNSUPPORTED, "map_lub_many: A = %zu > 1024 actors", A);
   if (V > (size_t)kWideVin) return fail(ctx, CRDT_EUNSUPPORTED, "map_lub_many: V = %zu > %d value slots", V, kWideVin);
@@ -552,7 +514,9 @@ int map_lub_wide(crdt_ctx *ctx, const crdt_map_batch *in, const size_t *def_off_
   p.o_vval = (u64 *)out->vval;
   p.o_nval = out->nval;
   p.o_flags = out->flags;
-  const size_t want = std::max<size_t>(std::max(out->Vstate, out->Vout), V);
+  p.deep = deep;
+  // (with a deep pass, Vstate > 16, the first pass's state is sized from Vout and V alone)
+  const size_t want = std::max<size_t>(std::max<size_t>(deep ? 0 : out->Vstate, out->Vout), V);
   const unsigned nt = (unsigned)std::min<size_t>(256, std::max<size_t>(64, (A + 4 * 64 - 1) / (4 * 64) * 64));
   const unsigned long long blocks = in->G * in->K;
   timing_begin(ctx, "map_fold");

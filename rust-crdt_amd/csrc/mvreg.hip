@@ -22,7 +22,13 @@
 // MVReg is unbounded, mvreg.rs:33-35) the same code runs with BLK = true: a workgroup of
 // ceil(A / 64) waves per register, thread t = actor t (one clock word per thread), every vote a
 // workgroup vote (__syncthreads_or), value slots up to 16 in and 16 in the working register.
+//
+// crdt_mvreg_lub_many with 17 <= out->Vstate <= 64 adds a deep pass: the first pass marks the registers
+// whose 16-value state overflowed (instead of flags bit 2), and mvreg_fold_deep_kernel folds each marked
+// register again, in replica order, with up to Vstate values held in LDS (mvreg_lds.hpp, the state the
+// Map fold's deep pass uses, map_deep.hip).
 #include "common.hpp"
+#include "mvreg_lds.hpp"
 
 namespace crdt {
 
@@ -211,6 +217,8 @@ struct MvFoldPlan {
   u64 *o_vclk, *o_vval;
   unsigned long long Vout;
   uint32_t *o_nval, *o_flags;
+  uint8_t *mark;  // (nullable) per group: the state overflowed, left to the deep pass
+  unsigned long long Vstate;  // the deep pass's slots
 };
 
 // One group's left fold (one wave per group); the next replica's slots are loaded while this
@@ -257,7 +265,30 @@ __global__ __launch_bounds__(BLK ? 1024 : 64) void mvreg_fold_kernel(MvFoldPlan 
   const int n = acc.store(p.o_vclk + g * p.Vout * p.A, p.o_vval + g * p.Vout, p.Vout, p.A, lane, nt);
   if (lane == 0) {
     if (p.o_nval) p.o_nval[g] = (uint32_t)n;
-    p.o_flags[g] = ((unsigned long long)n > p.Vout ? 1u : 0u) | (acc.ovf ? 4u : 0u);
+    const bool redo = p.mark && acc.ovf;  // the deep pass folds this register again
+    if (redo) p.mark[g] = 1;
+    p.o_flags[g] = redo ? 0u : ((unsigned long long)n > p.Vout ? 1u : 0u) | (acc.ovf ? 4u : 0u);
+  }
+}
+
+// The deep pass: one workgroup per marked register (the others exit at once), 64..256 threads with
+// actors striped over threads, the register in LDS; VIN = the incoming slots a merge's vote round is
+// unrolled for (V <= VIN).  Loops are bounded by R, V and Vstate; no workgroup waits for another.
+template <int VIN>
+__global__ __launch_bounds__(256) void mvreg_fold_deep_kernel(MvFoldPlan p) {
+  extern __shared__ u64 mv_deep_lds[];
+  __shared__ u64 red[kLdsMvRed];
+  const unsigned long long g = blockIdx.x;
+  if (!p.mark[g]) return;
+  LdsMv mv;
+  mv.init(mv_deep_lds, (unsigned)p.Vstate, (unsigned)p.A);
+  for (unsigned long long r = 0; r < p.R; ++r)
+    mv.template merge<VIN>(p.vclk + g * p.c_gs + r * p.c_rs, p.vval + g * p.v_gs + r * p.v_rs, p.V, red);
+  mv.store(p.o_vclk + g * p.Vout * p.A, p.o_vval + g * p.Vout, p.Vout);
+  if (threadIdx.x == 0) {
+    const unsigned long long n = (unsigned long long)mv.count();
+    if (p.o_nval) p.o_nval[g] = (uint32_t)n;
+    p.o_flags[g] = (n > p.Vout ? 1u : 0u) | (mv.ovf ? 4u : 0u);
   }
 }
 
@@ -450,8 +481,17 @@ int crdt_mvreg_lub_many(crdt_ctx *ctx, const crdt_mvreg_batch *in, crdt_mvreg_ou
   const size_t G = in->G, R = in->R, A = in->A, V = in->V, Vout = out->Vout;
   if (G == 0 || A == 0) return CRDT_OK;
   if (!out->vclk || !out->vval || !out->flags) return fail(ctx, CRDT_EINVAL, "mvreg_lub_many: NULL output");
-  if (Vout == 0 || Vout > (size_t)kMvMaxState)
-    return fail(ctx, CRDT_EUNSUPPORTED, "mvreg_lub_many: Vout = %zu not in [1, %d]", Vout, kMvMaxState);
+  // 17 <= Vstate <= 64: the deep pass redoes the registers whose 16-value state overflows
+  const bool deep = out->Vstate > (size_t)kMvMaxState;
+  if (out->Vstate > (size_t)kLdsMvMax)
+    return fail(ctx, CRDT_EUNSUPPORTED, "mvreg_lub_many: Vstate = %zu > %d", out->Vstate, kLdsMvMax);
+  const size_t vout_max = deep ? (size_t)kLdsMvMax : (size_t)kMvMaxState;
+  if (Vout == 0 || Vout > vout_max)
+    return fail(ctx, CRDT_EUNSUPPORTED, "mvreg_lub_many: Vout = %zu not in [1, %zu]", Vout, vout_max);
+  const size_t deep_lds = deep ? lds_mv_bytes(out->Vstate, A) : 0;
+  if (deep_lds + kLdsMvRed * sizeof(u64) > 160 * 1024)
+    return fail(ctx, CRDT_EUNSUPPORTED, "mvreg_lub_many: Vstate = %zu values of A = %zu actors need %zu bytes of LDS (> 160 KiB)",
+                out->Vstate, A, deep_lds + kLdsMvRed * sizeof(u64));
   if (R > 0 && V > 0 && (!in->vclk || !in->vval)) return fail(ctx, CRDT_EINVAL, "mvreg_lub_many: NULL input");
   if (A > 1024) return fail(ctx, CRDT_EUNSUPPORTED, "mvreg_lub_many: A = %zu > 1024 actors", A);
   if (V > 16) return fail(ctx, CRDT_EUNSUPPORTED, "mvreg_lub_many: V = %zu > 16 value slots", V);
@@ -475,7 +515,14 @@ int crdt_mvreg_lub_many(crdt_ctx *ctx, const crdt_mvreg_batch *in, crdt_mvreg_ou
   p.Vout = Vout;
   p.o_nval = out->nval;
   p.o_flags = out->flags;
-  const int VS = mv_vs(std::max<size_t>({Vout, out->Vstate, 2 * std::max<size_t>(V, 1)}));
+  p.Vstate = out->Vstate;
+  if (deep) {  // one marker byte per register in the context scratch
+    if (int rc = ensure_scratch(ctx, G)) return rc;
+    p.mark = static_cast<uint8_t *>(ctx->scratch);
+    if (int rc = device_fill(ctx, p.mark, G, 0)) return rc;
+  }
+  // (with a deep pass the first pass's state is sized from Vout and V alone)
+  const int VS = mv_vs(std::max<size_t>({Vout, deep ? 0 : out->Vstate, 2 * std::max<size_t>(V, 1)}));
   const bool wide = mv_wide(A, V);
   const int VI = wide ? mv_vi_wide(V) : mv_vi(V);
   timing_begin(ctx, "mvreg_fold");
@@ -485,6 +532,18 @@ int crdt_mvreg_lub_many(crdt_ctx *ctx, const crdt_mvreg_batch *in, crdt_mvreg_ou
                           : (apl == 2 ? launch_fold<2>(p, VS, VI, ctx->stream) : launch_fold<4>(p, VS, VI, ctx->stream));
   timing_end(ctx);
   if (e != hipSuccess) return hip_fail(ctx, e, "mvreg_fold_kernel launch");
+  if (deep) {  // same stream: no host synchronisation between the passes
+    const unsigned nt = (unsigned)std::min<size_t>(256, std::max<size_t>(64, (A + 4 * 64 - 1) / (4 * 64) * 64));
+    const void *fn = V <= 2 ? reinterpret_cast<const void *>(&mvreg_fold_deep_kernel<2>)
+                            : reinterpret_cast<const void *>(&mvreg_fold_deep_kernel<kLdsMvVin>);
+    if (deep_lds + kLdsMvRed * sizeof(u64) > 64 * 1024)  // beyond the default dynamic-LDS limit
+      CRDT_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)deep_lds));
+    timing_begin(ctx, "mvreg_fold_deep");
+    if (V <= 2) hipLaunchKernelGGL(mvreg_fold_deep_kernel<2>, dim3((unsigned)G), dim3(nt), deep_lds, ctx->stream, p);
+    else hipLaunchKernelGGL(mvreg_fold_deep_kernel<kLdsMvVin>, dim3((unsigned)G), dim3(nt), deep_lds, ctx->stream, p);
+    timing_end(ctx);
+    CRDT_HIP(ctx, hipGetLastError());
+  }
   return CRDT_OK;
 }
 

@@ -935,7 +935,9 @@ impl<K: Ord + Clone, V: Clone, A: Actor> BatchCvRDT for Map<K, MVReg<V, A>, A> {
         };
         // Vout grows until the fold fits (flags bit 0 = some key folded to more values); the fold
         // state starts at the library's choice (4 values: the scanned fast path) and widens to 8,
-        // then 16 values when a key overflows it (flags bit 2)
+        // then 16 values when a key overflows it (flags bit 2).  No step past 16: the deep pass
+        // (Vstate = 17..64) belongs to the device-memory entry points, and this CRDT_MEM_HOST ctx
+        // treats Vstate > 16 as 16, so a key with more than 16 concurrent values is still an error here
         let mut vout = 4usize;
         let mut vstate = 0usize;
         loop {
