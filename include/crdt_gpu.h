@@ -1090,6 +1090,64 @@ int crdt_gcounter_read(crdt_ctx *ctx, const uint64_t *in, size_t N, size_t A, si
 int crdt_pncounter_read(crdt_ctx *ctx, const uint64_t *in, size_t N, size_t A, size_t row_stride,
                         uint64_t *out);
 
+/* ---- batched ReadCtx queries (ctx.rs:8-55) -------------------------------------------------
+ * Every read of the reference returns ReadCtx { add_clock, rm_clock, val }; the contexts derived
+ * from it (derive_add_ctx / derive_rm_ctx, ctx.rs:40-55) are the only supported way to build the
+ * next Op.  These calls produce the dense form of those pieces in device memory, so read ->
+ * derive ctx -> op -> *_apply_batch never leaves the device.  Every output element is written on
+ * every call.  Per-query status[q] (device u32): bit 1 = a state index, member, key or actor out
+ * of range (the query's outputs are those of an absent element: zeros).
+ *
+ * Orswot::read / read_ctx (orswot.rs:264-279) / Map::is_empty, len and read_ctx (map.rs:233-249,
+ * :301-307) as a presence scan: N states of M (K) rows of A words, row (s, m) at
+ * entries + s*entry_sstride + m*entry_mstride (the crdt_orswot_states layout; a Map's ec with
+ * ec_kstride = A, ec_sstride = ec_stride).  members[s*Mw + w] (Mw = ceil(M/64)) has bit b set iff
+ * row 64w + b is non-zero (member / key present); bits past M are 0.  len[s] (may be NULL) = the
+ * number of present rows; Map::is_empty is len[s] == 0.  add_clock = rm_clock = the state's clock
+ * (the caller has it).  crdt_map_read serves Map<K, MVReg> and every value-typed Map (all mark an
+ * absent key by an all-zero ec row).  Rows are read with 16-byte loads when A, both strides and
+ * the base pointer keep every row 16-byte aligned, with 8-byte loads otherwise. */
+int crdt_orswot_read(crdt_ctx *ctx, const uint64_t *entries, size_t entry_mstride, size_t entry_sstride, size_t N,
+                     size_t M, size_t A, uint64_t *members /* [N][Mw] */, uint32_t *len /* [N] or NULL */);
+int crdt_map_read(crdt_ctx *ctx, const uint64_t *ec, size_t ec_kstride, size_t ec_sstride, size_t N, size_t K,
+                  size_t A, uint64_t *keys /* [N][Kw] */, uint32_t *len /* [N] or NULL */);
+
+/* Orswot::contains (orswot.rs:253-262) of Q queries (state_idx[q], member[q]) (device u32):
+ * val[q] = 1 iff the member is present, rm_clock + q*rm_stride = the member's dot clock (the
+ * ReadCtx's rm_clock; all zeros when absent).  add_clock is the clock row of state state_idx[q]. */
+int crdt_orswot_contains(crdt_ctx *ctx, const uint64_t *entries, size_t entry_mstride, size_t entry_sstride,
+                         size_t N, size_t M, size_t A, const uint32_t *state_idx, const uint32_t *member, size_t Q,
+                         uint8_t *val /* [Q] */, uint64_t *rm_clock, size_t rm_stride, uint32_t *status /* [Q] */);
+
+/* MVReg::read / read_ctx (mvreg.rs:183-215) of the N registers of `regs` (crdt_mvreg_states):
+ * clock + i*clock_stride = the pointwise max of the non-empty slot clocks (add_clock = rm_clock,
+ * mvreg.rs:207-215), vals[i*V ..] (may be NULL) = the values of the non-empty slots in Vec order,
+ * the rest 0, nval[i] (may be NULL) = their count.  V <= 64. */
+int crdt_mvreg_read(crdt_ctx *ctx, const crdt_mvreg_states *regs, uint64_t *clock, size_t clock_stride,
+                    uint64_t *vals /* [N][V] or NULL */, uint32_t *nval /* [N] or NULL */);
+
+/* Map::get (map.rs:251-262) of Q queries (state_idx[q], key[q]) (device u32) on Map<K, MVReg>
+ * states: present[q] = 1 iff the key has an entry, rm_clock[q*A ..] = its entry clock (zeros when
+ * absent), the key's register compacted in Vec order (non-empty slots first, the rest zeroed):
+ * vclk[(q*V + j)*A ..], vval[q*V + j], nval[q]; val_clock[q*A ..] = the join of its slot clocks,
+ * the clock a following MVReg::read of that value returns (mvreg.rs:207-215).  An absent key has
+ * no register (val = None): nval 0, zeros.  add_clock is the clock row of state state_idx[q].
+ * V <= 64. */
+int crdt_map_get(crdt_ctx *ctx, const crdt_map_states *states, const uint32_t *state_idx, const uint32_t *key,
+                 size_t Q, uint8_t *present /* [Q] */, uint64_t *rm_clock /* [Q][A] */, uint64_t *vclk /* [Q][V][A] */,
+                 uint64_t *vval /* [Q][V] */, uint32_t *nval /* [Q] */, uint64_t *val_clock /* [Q][A] */,
+                 uint32_t *status /* [Q] */);
+
+/* ReadCtx::derive_add_ctx (ctx.rs:40-48: dot = add_clock.inc(actor); add_clock.apply(dot)) of Q
+ * clock rows: out_clock + q*out_stride = clock + q*clock_stride with [actor[q]] += 1, counter[q] =
+ * that new value (the AddCtx's dot is (actor[q], counter[q])).  out_clock may be clock itself
+ * (same pointer and stride).  status[q]: bit 1 = actor[q] >= A, bit 2 = the actor's counter is
+ * already UINT64_MAX; in both cases the row is copied unchanged and counter[q] = 0.
+ * ReadCtx::derive_rm_ctx (ctx.rs:51-55) needs no call: its clock is the rm_clock row. */
+int crdt_vclock_derive_add(crdt_ctx *ctx, const uint64_t *clock, size_t clock_stride, size_t Q, size_t A,
+                           const uint32_t *actor, uint64_t *out_clock, size_t out_stride, uint64_t *counter /* [Q] */,
+                           uint32_t *status /* [Q] */);
+
 /* ---- batched CmRDT::apply ---------------------------------------------------
  * Apply n_ops ops to N dense states; op i targets state state_idx[i] (row at
  * states + state_idx[i]*row_stride).  The ops of these types are per-cell joins, so they commute:

@@ -61,6 +61,8 @@ EXPORTS = (
     "crdt_map_nested_apply_batch", "crdt_map_nested_forget_batch", "crdt_map_nested_ingest", "crdt_map_nested_egress",
     "crdt_map_counter_merge_batch", "crdt_map_orswot_merge_batch", "crdt_map_nested_merge_batch",
     "crdt_map_counter_ingest", "crdt_map_counter_egress", "crdt_map_orswot_ingest", "crdt_map_orswot_egress",
+    "crdt_orswot_read", "crdt_orswot_contains", "crdt_mvreg_read", "crdt_map_read", "crdt_map_get",
+    "crdt_vclock_derive_add",
 )
 
 
@@ -367,6 +369,14 @@ _SIGS.update({
                                      ctypes.c_int),
     "crdt_orswot_lub_many_sharded_doff": ([P, ctypes.POINTER(OrswotBatch), P, S, ctypes.POINTER(OrswotShardedOut)],
                                           ctypes.c_int),
+})
+_SIGS.update({  # batched ReadCtx queries (csrc/read.hip)
+    "crdt_orswot_read": ([P, P, S, S, S, S, S, P, P], ctypes.c_int),
+    "crdt_map_read": ([P, P, S, S, S, S, S, P, P], ctypes.c_int),
+    "crdt_orswot_contains": ([P, P, S, S, S, S, S, P, P, S, P, P, S, P], ctypes.c_int),
+    "crdt_mvreg_read": ([P, ctypes.POINTER(MVRegStates), P, S, P, P], ctypes.c_int),
+    "crdt_map_get": ([P, ctypes.POINTER(MapStates), P, P, S, P, P, P, P, P, P, P], ctypes.c_int),
+    "crdt_vclock_derive_add": ([P, P, S, S, S, P, P, S, P, P], ctypes.c_int),
 })
 for _t in ("vclock", "gcounter", "pncounter", "gset"):
     _SIGS[f"crdt_{_t}_lub_many_sharded"] = ([P, P, S, S, S, S, S, P], ctypes.c_int)

@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from . import _abi
+from . import readctx as _rc
 from .context import Context
 
 
@@ -1372,3 +1373,82 @@ def nested_merge_batch(me, other, ctx: Optional[Context] = None) -> torch.Tensor
     sa, N, K, A = _nested_states(me, what)
     sb, _, _, _ = _nested_states(other, what)
     return _vm_call(ctx, "crdt_map_nested_merge_batch", sa, sb, me, other, N, A, K, what)
+
+
+# ---------------------------------------------------------------------------------------------
+# Batched reads: Map::is_empty / len / get / read_ctx (map.rs:233-307) as ReadCtx (readctx.py)
+# ---------------------------------------------------------------------------------------------
+class MapGetVal(NamedTuple):
+    """val of map.get: the queried keys' registers, compacted in Vec order."""
+    present: torch.Tensor    # (Q,) uint8: the key has an entry (Map::get -> Some)
+    vclk: torch.Tensor       # (Q, V, A) slot clocks, non-empty slots first, the rest zero
+    vval: torch.Tensor       # (Q, V)
+    nval: torch.Tensor       # (Q,) int32
+    val_clock: torch.Tensor  # (Q, A): the join of the slot clocks (what MVReg::read of the value returns)
+
+
+def read(clock: torch.Tensor, ec: torch.Tensor, ctx: Optional[Context] = None) -> "_rc.ReadCtx":
+    """Map::len / is_empty / read_ctx (map.rs:233-249, :301-307) of N states of any value type from
+    their entry clocks: ReadCtx(add_clock = rm_clock = clock (N, A), val = (keys (N, ceil(K/64)) int64
+    bitmap: bit k set iff key k has an entry, len (N,) int32)); is_empty is len == 0."""
+    _rc.check_args("map.read", [(clock, "clock"), (ec, "ec")])
+    if clock.dim() != 2 or ec.dim() != 3:
+        raise ValueError("map.read: clock (N, A), ec (N, K, A) expected")
+    N, A = clock.shape
+    K = ec.shape[1]
+    if (ec.shape[0] != N or ec.shape[2] != A or (K > 1 and ec.stride(1) < A)
+            or (N > 1 and ec.stride(0) < K * ec.stride(1))):
+        raise ValueError(f"map.read: ec {tuple(ec.shape)} / clock {tuple(clock.shape)} mismatch")
+    ctx = ctx or Context.default(clock.device.index)
+    ctx.check_tensor(clock, "map.read(clock)")
+    ctx.check_tensor(ec, "map.read(ec)")
+    keys = torch.empty((N, (K + 63) // 64), dtype=torch.int64, device=clock.device)
+    n = torch.empty(N, dtype=torch.int32, device=clock.device)
+    ctx.call("crdt_map_read", ec.data_ptr(), ec.stride(1), ec.stride(0), N, K, A, keys.data_ptr(), n.data_ptr())
+    return _rc.ReadCtx(clock, clock, (keys, n))
+
+
+def get(states, state_idx: torch.Tensor, key: torch.Tensor, ctx: Optional[Context] = None):
+    """Map::get (map.rs:251-262) of Q queries (state_idx[q], key[q]) ((Q,) int32 device tensors) on
+    Map<K, MVReg> states: `states` is a MapLub, a MapStates, or anything with their clock (N, A) /
+    ec (N, K, A) / vclk (N, K, V, A) / vval (N, K, V) tensors.  Returns (ReadCtx(add_clock (Q, A) =
+    the queried states' clocks, rm_clock (Q, A) = the entry clocks, zeros when absent, val =
+    MapGetVal), status (Q,) int32: bit 1 = state index or key out of range)."""
+    clock, ec, vclk, vval = states.clock, states.ec, states.vclk, states.vval
+    _rc.check_args("map.get", [(clock, "clock"), (ec, "ec"), (vclk, "vclk"), (vval, "vval")],
+                   [(state_idx, "state_idx"), (key, "key")])
+    if clock.dim() != 2 or vclk.dim() != 4:
+        raise ValueError("map.get: clock (N, A), ec (N, K, A), vclk (N, K, V, A), vval (N, K, V) expected")
+    N, A = clock.shape
+    K, V = vclk.shape[1], vclk.shape[2]
+    if (tuple(ec.shape) != (N, K, A) or tuple(vclk.shape) != (N, K, V, A) or tuple(vval.shape) != (N, K, V)
+            or (K > 1 and ec.stride(1) != A) or (V > 1 and vclk.stride(2) != A) or (K > 1 and vclk.stride(1) != V * A)
+            or (K > 1 and vval.stride(1) != V)):
+        raise ValueError("map.get: per-state blocks must be packed (K, A) / (K, V, A) / (K, V)")
+    Q = state_idx.shape[0]
+    if key.shape[0] != Q:
+        raise ValueError("map.get: state_idx and key differ in length")
+    ctx = ctx or Context.default(clock.device.index)
+    for t_, nm in ((clock, "clock"), (ec, "ec"), (vclk, "vclk"), (vval, "vval")):
+        ctx.check_tensor(t_, f"map.get({nm})")
+    for t_, nm in ((state_idx, "state_idx"), (key, "key")):
+        ctx.check_tensor(t_, f"map.get({nm})", _rc.U32_DTYPES)
+    st = _abi.MapStates()
+    st.N, st.K, st.A, st.V = N, K, A, V
+    st.clock, st.clock_stride = clock.data_ptr(), clock.stride(0)
+    st.ec, st.ec_stride = ec.data_ptr(), ec.stride(0) if N > 1 else K * A
+    st.vclk, st.vclk_stride = vclk.data_ptr(), vclk.stride(0) if N > 1 else K * V * A
+    st.vval, st.vval_stride = vval.data_ptr(), vval.stride(0) if N > 1 else K * V
+    dev = clock.device
+    present = torch.empty(Q, dtype=torch.uint8, device=dev)
+    rm_clock = torch.empty((Q, A), dtype=clock.dtype, device=dev)
+    oclk = torch.empty((Q, V, A), dtype=vclk.dtype, device=dev)
+    oval = torch.empty((Q, V), dtype=vval.dtype, device=dev)
+    nval = torch.empty(Q, dtype=torch.int32, device=dev)
+    val_clock = torch.empty((Q, A), dtype=clock.dtype, device=dev)
+    status = torch.empty(Q, dtype=torch.int32, device=dev)
+    ctx.call("crdt_map_get", ctypes.byref(st), state_idx.data_ptr(), key.data_ptr(), Q, present.data_ptr(),
+             rm_clock.data_ptr(), oclk.data_ptr(), oval.data_ptr(), nval.data_ptr(), val_clock.data_ptr(),
+             status.data_ptr())
+    return (_rc.ReadCtx(_rc.gather_rows(ctx, clock, state_idx), rm_clock,
+                        MapGetVal(present, oclk, oval, nval, val_clock)), status)

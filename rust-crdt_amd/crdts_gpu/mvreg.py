@@ -7,6 +7,7 @@ Dense register (the value layout of the Map entry points): slots in Vec order,
     lub_many(vclk (G, R, V, A) or (R, V, A), vval)  acc = MVReg::new(); for r: acc.merge(r)  (mvreg.rs:112-128)
     merge_batch(self (N, V, A), other)               self[i].merge(other[i]), in place
     apply_batch(vclk (N, V, A), vval, ops)           reg[i].apply(op) for its ops in order   (mvreg.rs:130-166)
+    read(vclk (N, V, A), vval)                       reg[i].read() as a ReadCtx              (mvreg.rs:183-215)
 """
 from __future__ import annotations
 
@@ -17,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _abi
+from . import readctx as _rc
 from .context import Context
 
 
@@ -139,3 +141,22 @@ def apply_batch(vclk: torch.Tensor, vval: torch.Tensor, ops: MVRegOpBatch, ctx: 
     status = torch.empty(st.N, dtype=torch.int32, device=vclk.device)
     ctx.call("crdt_mvreg_apply_batch", ctypes.byref(st), ctypes.byref(o), status.data_ptr())
     return status
+
+
+def read(vclk: torch.Tensor, vval: torch.Tensor, ctx: Optional[Context] = None) -> "_rc.ReadCtx":
+    """MVReg::read (mvreg.rs:183-215) of N registers (vclk (N, V, A), vval (N, V)): ReadCtx(add_clock
+    = rm_clock = the join of the non-empty slots' clocks (N, A), val = (vals (N, V) int64: the values
+    in Vec order, the rest 0, nval (N,) int32))."""
+    _rc.check_args("mvreg.read", [(vclk, "vclk"), (vval, "vval")])
+    if vclk.dim() != 3 or vval.dim() != 2 or tuple(vclk.shape[:2]) != tuple(vval.shape):
+        raise ValueError("mvreg.read: vclk (N, V, A) and vval (N, V) expected")
+    N, V, A = vclk.shape
+    if V > 1 and vclk.stride(1) != A:
+        raise ValueError("mvreg.read: each register's slots must be packed")
+    ctx = ctx or Context.default(vclk.device.index)
+    st = _states(ctx, vclk, vval, "mvreg.read")
+    clock = torch.empty((N, A), dtype=vclk.dtype, device=vclk.device)
+    vals = torch.empty((N, V), dtype=vval.dtype, device=vclk.device)
+    nval = torch.empty(N, dtype=torch.int32, device=vclk.device)
+    ctx.call("crdt_mvreg_read", ctypes.byref(st), clock.data_ptr(), A, vals.data_ptr(), nval.data_ptr())
+    return _rc.ReadCtx(clock, clock, (vals, nval))

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _abi
+from . import readctx as _rc
 from .context import Context, dptr
 
 
@@ -397,3 +398,56 @@ def merge_batch(self_states: OrswotStates, other: OrswotStates, ctx: Optional[Co
     status = torch.empty(a.N, dtype=torch.int32, device=self_states.clock.device)
     ctx.call("crdt_orswot_merge_batch", ctypes.byref(a), ctypes.byref(b), dptr(status))
     return status
+
+
+# ---------------------------------------------------------------------------------------------
+# Batched reads: Orswot::read / contains (orswot.rs:253-279) as ReadCtx (readctx.py)
+# ---------------------------------------------------------------------------------------------
+def _check_read(clock, entries, what, index=()):
+    """-> (N, M, A) of clock (N, A) / entries (N, M, A) in the apply_batch layout."""
+    _rc.check_args(what, [(clock, "clock"), (entries, "entries")], index)
+    if clock.dim() != 2 or entries.dim() != 3:
+        raise ValueError(f"{what}: clock (N, A), entries (N, M, A) expected")
+    N, A = clock.shape
+    M = entries.shape[1]
+    if (entries.shape[0] != N or entries.shape[2] != A or (M > 1 and entries.stride(1) < A)
+            or (N > 1 and entries.stride(0) < M * entries.stride(1))):
+        raise ValueError(f"{what}: entries {tuple(entries.shape)} / clock {tuple(clock.shape)} mismatch")
+    return N, M, A
+
+
+def read(clock: torch.Tensor, entries: torch.Tensor, ctx: Optional[Context] = None) -> "_rc.ReadCtx":
+    """Orswot::read (orswot.rs:264-271) of N states: ReadCtx(add_clock = rm_clock = clock,
+    val = (members (N, ceil(M/64)) int64 bitmap: bit m set iff member m is present, len (N,) int32))."""
+    N, M, A = _check_read(clock, entries, "orswot.read")
+    ctx = ctx or Context.default(clock.device.index)
+    ctx.check_tensor(clock, "orswot.read(clock)")
+    ctx.check_tensor(entries, "orswot.read(entries)")
+    members = torch.empty((N, (M + 63) // 64), dtype=torch.int64, device=clock.device)
+    n = torch.empty(N, dtype=torch.int32, device=clock.device)
+    ctx.call("crdt_orswot_read", dptr(entries), entries.stride(1), entries.stride(0), N, M, A, dptr(members), dptr(n))
+    return _rc.ReadCtx(clock, clock, (members, n))
+
+
+def contains(clock: torch.Tensor, entries: torch.Tensor, state_idx: torch.Tensor, member: torch.Tensor,
+             ctx: Optional[Context] = None):
+    """Orswot::contains (orswot.rs:253-262) of Q queries (state_idx[q], member[q]) ((Q,) int32 device
+    tensors).  Returns (ReadCtx(add_clock (Q, A) = the queried states' clocks, rm_clock (Q, A) = the
+    members' dot clocks, zeros when absent, val (Q,) uint8), status (Q,) int32: bit 1 = state index
+    or member out of range)."""
+    N, M, A = _check_read(clock, entries, "orswot.contains", [(state_idx, "state_idx"), (member, "member")])
+    Q = state_idx.shape[0]
+    if member.shape[0] != Q:
+        raise ValueError("orswot.contains: state_idx and member differ in length")
+    ctx = ctx or Context.default(clock.device.index)
+    for t, nm in ((clock, "clock"), (entries, "entries")):
+        ctx.check_tensor(t, f"orswot.contains({nm})")
+    for t, nm in ((state_idx, "state_idx"), (member, "member")):
+        ctx.check_tensor(t, f"orswot.contains({nm})", _rc.U32_DTYPES)
+    dev = clock.device
+    val = torch.empty(Q, dtype=torch.uint8, device=dev)
+    rm_clock = torch.empty((Q, A), dtype=clock.dtype, device=dev)
+    status = torch.empty(Q, dtype=torch.int32, device=dev)
+    ctx.call("crdt_orswot_contains", dptr(entries), entries.stride(1), entries.stride(0), N, M, A, dptr(state_idx),
+             dptr(member), Q, dptr(val), dptr(rm_clock), A, dptr(status))
+    return _rc.ReadCtx(_rc.gather_rows(ctx, clock, state_idx), rm_clock, val), status

@@ -121,6 +121,10 @@ struct Tune {
   int map_apply_pf = 1;        // Map apply (16-lane groups): the next op's entry-clock row prefetched with its
                                //     Put / rm clock; absent keys skip their value rows (0: round-3 form;
                                //     1.28 vs 1.81 ms, profiles/r04_map_apply_pf_ab.log)
+  int read_bpc = 0;            // presence scan (read.hip): workgroups per CU of a grid-stride loop (0: one wave
+                               //     per output word, no loop)
+  int read_unroll = 8;         // ... loads per lane in flight before the first is tested (4, 8)
+  int read_nt = 1;             // ... non-temporal loads (the entries are read once)
 };
 
 struct PendingTiming {

@@ -248,6 +248,9 @@ static void apply_tune(crdt_ctx *ctx, const char *t) {
       else if (k == "mapf") ctx->tune.map_apply_pf = v != 0;
       else if (k == "mameta") ctx->tune.map_apply_meta = v != 0;
       else if (k == "rbpc" && v > 0) ctx->tune.rows_blocks_per_cu = v;
+      else if (k == "rdbpc" && v >= 0 && v <= 4096) ctx->tune.read_bpc = v;
+      else if (k == "rdu" && (v == 4 || v == 8)) ctx->tune.read_unroll = v;
+      else if (k == "rdnt") ctx->tune.read_nt = v != 0;
       else if (k == "hot" && v >= 0 && v <= 64) ctx->tune.apply_hot_slots = v;
       else if (k == "mhot" && v >= 0) ctx->tune.map_apply_hot = v;
       else if (k == "mfv2") ctx->tune.map_forget_vec2 = v != 0;
