@@ -47,6 +47,8 @@ struct KernelTimer {
 struct Tune {
   int lub_blocks_per_cu = 1;
   int lub_grid = 0;  // >0: total workgroups target (overrides lub_blocks_per_cu)
+  int lub_persist_grid = 0;  // >0: workgroups of the persistent multi-segment launch (default: cu_count x lub_blocks_per_cu)
+  int lub_chunk_bytes = 512 << 10;  // persistent multi-segment launch: bytes per chunk of its dynamic tail (0: no tail)
   int lub_min_steps = 16;
   int lub_interleave = 0;
   int lub_unroll = 8;

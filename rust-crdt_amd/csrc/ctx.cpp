@@ -205,6 +205,8 @@ static void apply_tune(crdt_ctx *ctx, const char *t) {
       else if (k == "unroll" && (v == 4 || v == 8 || v == 16 || v == 32)) ctx->tune.lub_unroll = v;
       else if (k == "nt") ctx->tune.lub_nt = v != 0;
       else if (k == "grid" && v > 0) ctx->tune.lub_grid = v;
+      else if (k == "lubpg" && v >= 0) ctx->tune.lub_persist_grid = v;
+      else if (k == "lubchunk" && v >= 0) ctx->tune.lub_chunk_bytes = v;
       else if (k == "mbpc" && v > 0) ctx->tune.merge_blocks_per_cu = v;
       else if (k == "mrows" && (v == 0 || v == 1)) ctx->tune.merge_rows = v;
       else if (k == "obpc" && v > 0) ctx->tune.orswot_blocks_per_cu = v;

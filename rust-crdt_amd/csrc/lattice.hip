@@ -126,9 +126,44 @@ __device__ __forceinline__ bool arrive_last(unsigned *counter, unsigned expected
   return *s_flag != 0;
 }
 
-// One launch = the whole lub.  Block b -> (unit u = g*ncolblk + cb, slice s).
+// Partial rows a lane of the last arriver keeps in flight in the level-1 / level-2 combines: these
+// reads are the serial end of every launch, and a cluster's 32 rows take two round trips at 16
+// (eight at 4).
+constexpr int kLubCombineU = 16;
+
+// Fold n >= 1 partial rows spaced `step` vectors apart, always kLubCombineU loads in flight: a
+// batch past the end re-reads the last row instead of branching (the joins are idempotent), so
+// a short fold (8 cluster partials, say) is one round trip, not one per row.
+template <Op OP, typename VT>
+__device__ __forceinline__ VT fold_partials(const VT *p, size_t n, long long step) {
+  constexpr int U = kLubCombineU;
+  VT acc = vzero<VT>();
+  for (size_t i = 0; i < n; i += U) {
+    const size_t rem = n - i;
+    VT v[U];
+#pragma unroll
+    for (int k = 0; k < U; ++k) v[k] = p[(long long)((size_t)k < rem ? (size_t)k : rem - 1) * step];
+#pragma unroll
+    for (int k = 0; k < U; ++k) acc = vjoin<OP>(acc, v[k]);
+    p += U * step;
+  }
+  return acc;
+}
+
+// Rows r0, r0 + rstep, ... < rend of group g folded at vector column col.
 template <Op OP, int V, int U, bool NT, typename VT>
-__device__ __forceinline__ void lub_stream_body(const LubPlan &p, unsigned b, VT *red, int &s_flag) {
+__device__ __forceinline__ VT lub_fold_range(const LubPlan &p, size_t g, int col, unsigned long long r0,
+                                             unsigned long long rend, unsigned long long rstep) {
+  if (r0 >= rend) return vzero<VT>();
+  const size_t n = (rend - r0 + rstep - 1) / rstep;
+  const VT *src = reinterpret_cast<const VT *>(p.in + g * p.gstride + r0 * p.rstride) + col;
+  return fold_rows<OP, VT, U, NT>(src, n, (long long)rstep * p.rstride / V);
+}
+
+// The end of block b once its threads hold the fold of its rows in `acc`: combine the block's
+// row-lanes, publish the partial row, and (last arrivers only) run the two combine levels.
+template <Op OP, typename VT>
+__device__ __forceinline__ void lub_finish(const LubPlan &p, unsigned b, VT acc, VT *red, int &s_flag) {
   const int l = threadIdx.x;
   const int s = b % p.S;
   const unsigned u = b / p.S;
@@ -137,27 +172,6 @@ __device__ __forceinline__ void lub_stream_body(const LubPlan &p, unsigned b, VT
   const int cl = l % p.PW;
   const int rsub = l / p.PW;
   const int col = cb * kBlock + cl;
-  const bool active = rsub < p.TR && col < p.Wv;
-
-  VT acc = vzero<VT>();
-  if (active) {
-    unsigned long long r0, rend, rstep;
-    if (p.interleave) {
-      r0 = (unsigned long long)s * p.TR + rsub;
-      rend = p.R;
-      rstep = (unsigned long long)p.S * p.TR;
-    } else {
-      const unsigned long long rbeg = (unsigned long long)s * p.Rs;
-      rend = min(p.R, rbeg + p.Rs);
-      r0 = rbeg + rsub;
-      rstep = p.TR;
-    }
-    if (r0 < rend) {
-      const size_t n = (rend - r0 + rstep - 1) / rstep;
-      const VT *src = reinterpret_cast<const VT *>(p.in + g * p.gstride + r0 * p.rstride) + col;
-      acc = fold_rows<OP, VT, U, NT>(src, n, (long long)rstep * p.rstride / V);
-    }
-  }
   acc = block_rows_combine<OP>(acc, red, l, p.PW, p.TR);
   const bool writer = (l < p.PW) && col < p.Wv;
   if (p.S == 1) {
@@ -179,8 +193,7 @@ __device__ __forceinline__ void lub_stream_body(const LubPlan &p, unsigned b, VT
       const int r0 = rsub;
       if (r0 < csize) {
         const size_t n = (csize - r0 + TRc - 1) / TRc;
-        acc = fold_rows<OP, VT, 4, false>(part + ((size_t)u * p.S + c * p.CL + r0) * p.PW + cl, n,
-                                          (long long)TRc * p.PW);
+        acc = fold_partials<OP>(part + ((size_t)u * p.S + c * p.CL + r0) * p.PW + cl, n, (long long)TRc * p.PW);
       }
     }
   }
@@ -198,11 +211,34 @@ __device__ __forceinline__ void lub_stream_body(const LubPlan &p, unsigned b, VT
   acc = vzero<VT>();
   if (rsub < p.TR && col < p.Wv && rsub < p.ncl) {
     const size_t n = (p.ncl - rsub + p.TR - 1) / p.TR;
-    acc = fold_rows<OP, VT, 4, false>(cpart + ((size_t)u * p.ncl + rsub) * p.PW + cl, n,
-                                      (long long)p.TR * p.PW);
+    acc = fold_partials<OP>(cpart + ((size_t)u * p.ncl + rsub) * p.PW + cl, n, (long long)p.TR * p.PW);
   }
   acc = block_rows_combine<OP>(acc, red, l, p.PW, p.TR);
   if (writer) store_out<OP>(p, g, col, acc);
+}
+
+// One launch = the whole lub.  Block b -> (unit u = g*ncolblk + cb, slice s).
+template <Op OP, int V, int U, bool NT, typename VT>
+__device__ __forceinline__ void lub_stream_body(const LubPlan &p, unsigned b, VT *red, int &s_flag) {
+  const int l = threadIdx.x;
+  const int s = b % p.S;
+  const unsigned u = b / p.S;
+  const int cb = u % p.ncolblk;
+  const size_t g = u / p.ncolblk;
+  const int rsub = l / p.PW;
+  const int col = cb * kBlock + l % p.PW;
+
+  VT acc = vzero<VT>();
+  if (rsub < p.TR && col < p.Wv) {
+    if (p.interleave) {
+      acc = lub_fold_range<OP, V, U, NT, VT>(p, g, col, (unsigned long long)s * p.TR + rsub, p.R,
+                                             (unsigned long long)p.S * p.TR);
+    } else {
+      const unsigned long long rbeg = (unsigned long long)s * p.Rs;
+      acc = lub_fold_range<OP, V, U, NT, VT>(p, g, col, rbeg + rsub, min(p.R, rbeg + p.Rs), p.TR);
+    }
+  }
+  lub_finish<OP>(p, b, acc, red, s_flag);
 }
 
 template <Op OP, int V, int U, bool NT = true>
@@ -213,27 +249,171 @@ __global__ __launch_bounds__(kBlock) void lub_stream_kernel(LubPlan p) {
   lub_stream_body<OP, V, U, NT, VT>(p, blockIdx.x, red, s_flag);
 }
 
-// Several lubs of one join op in ONE launch (crdt_lub_many_multi): segment i owns blocks
-// [start[i], start[i+1]) and runs exactly the single-lub body on its own plan, so the launch pays
-// one ramp and one tail instead of one per lub.
+// Several lubs of one join op in ONE persistent launch (crdt_lub_many_multi): segment i owns blocks
+// [start[i], start[i+1]) of one concatenated list and every block runs exactly the single-lub body
+// on its segment's plan.  The grid is min(blocks, one workgroup per CU) and workgroup w runs blocks
+// w, w + grid, w + 2*grid, ...: the CU never holds more than its own stream, and where the segments
+// were planned for the same grid every workgroup reads the same bytes (one slice of each segment).
+// No block waits for another (the last arriver of a cluster combines, whoever it is), so the
+// workgroups need not be co-resident and any grid >= 1 completes.  Where the launch's shape allows
+// (lub_plan_tail), the blocks of the last round share the end of their rows through a ticket
+// counter (lub_tail_block) so that the workgroups finish together.
 constexpr int kLubMultiMax = 8;
 struct LubMulti {
   LubPlan p[kLubMultiMax];
   unsigned start[kLubMultiMax + 1];
   int n;
+  // Dynamic tail (lub_plan_tail): the blocks of the last round, b >= tail_first, all slices of the
+  // last segment, fold only the first tail_rstat rows of their slice themselves; the rest is
+  // tail_nch chunks of tail_rc rows per slice, handed out through *ticket.  tail_nch == 0: none.
+  unsigned *ticket;
+  unsigned tail_first, tail_nch;
+  unsigned long long tail_rstat, tail_rc;
+#ifdef LUB_STATS
+  unsigned long long *stats;  // [total blocks][4]: see LubStat
+#endif
 };
+
+#ifdef LUB_STATS
+// -DLUB_STATS (scripts/build_variant.sh stats lattice.hip -DLUB_STATS; never the timed build): every
+// block of a fused launch records who ran it, where and when; the host writes the records of the
+// last launch to the file named by LUB_STATS_OUT (scripts/lub_stats.py reads it).
+struct LubStat {
+  unsigned long long t0, t1;  // wall_clock64() (100 MHz) at entry / exit of the block
+  unsigned wg, seg, hw_id, xcc_id;
+  __device__ __forceinline__ void begin(unsigned w, int i) {
+    wg = w;
+    seg = (unsigned)i;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_id));
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc_id));
+    t0 = wall_clock64();
+  }
+  __device__ __forceinline__ void end(unsigned long long *stats, unsigned b) {
+    t1 = wall_clock64();
+    if (threadIdx.x == 0) {
+      unsigned long long *o = stats + 4ull * b;
+      o[0] = t0;
+      o[1] = t1;
+      o[2] = (unsigned long long)wg | ((unsigned long long)seg << 32);
+      o[3] = (unsigned long long)hw_id | ((unsigned long long)xcc_id << 32);
+    }
+  }
+};
+
+static int lub_stats_begin(crdt_ctx *ctx, LubMulti &m, size_t blocks) {
+  static unsigned long long *buf = nullptr;
+  static size_t cap = 0;
+  if (blocks > cap) {
+    if (buf) (void)hipFree(buf);
+    cap = 0;
+    CRDT_HIP(ctx, hipMalloc(&buf, blocks * 32));
+    cap = blocks;
+  }
+  m.stats = buf;
+  return CRDT_OK;
+}
+
+static int lub_stats_dump(crdt_ctx *ctx, const LubMulti &m, size_t blocks, unsigned grid) {
+  const char *path = getenv("LUB_STATS_OUT");
+  if (!path) return CRDT_OK;
+  std::vector<unsigned long long> h(blocks * 4);
+  CRDT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  CRDT_HIP(ctx, hipMemcpy(h.data(), m.stats, blocks * 32, hipMemcpyDeviceToHost));
+  FILE *f = fopen(path, "w");
+  if (!f) return fail(ctx, CRDT_EINVAL, "LUB_STATS_OUT: cannot write %s", path);
+  fprintf(f, "# grid %u blocks %zu segments %d cu_count %d\n# block seg wg t0 t1 xcc hw_id\n", grid, blocks, m.n,
+          ctx->cu_count);
+  for (size_t b = 0; b < blocks; ++b)
+    fprintf(f, "%zu %llu %llu %llu %llu %llu %llu\n", b, h[4 * b + 2] >> 32, h[4 * b + 2] & 0xffffffffull, h[4 * b],
+            h[4 * b + 1], h[4 * b + 3] >> 32, h[4 * b + 3] & 0xffffffffull);
+  fclose(f);
+  return CRDT_OK;
+}
+#endif
+
+// A block of the last round with a dynamic tail.  The workgroups do not finish together (their
+// exits spread over ~5% of the launch at the bench shape: each CU gets what the fabric gives it),
+// so the last eighth of the launch's bytes is not owned by anybody: it is cut into chunks
+// (>= 512 KiB each) of the last segment's slices and a workgroup that has folded the static part of
+// its slice takes chunks from one agent-scope ticket counter until none is left.  The joins are
+// associative, commutative and idempotent and every tail slice belongs to the same unit (one
+// group, one column block), so a chunk of ANY slice joins into this workgroup's accumulators and
+// the partial row it then publishes for its own slice is as good as any other split of the rows:
+// the scratch layout, the counters and the combine are those of the static plan and the result is
+// bit for bit the same.  Nobody waits: the next ticket is requested before the current chunk is
+// folded (its latency hides behind the chunk's first loads) and a workgroup that draws a ticket
+// past the end goes on to publish.  Every workgroup draws exactly one such ticket, so the draw
+// numbered tickets + workgroups - 1 is the last one of the launch and resets the counter.
+template <Op OP, int V, int U, typename VT>
+__device__ __forceinline__ void lub_tail_block(const LubMulti &m, unsigned b, VT *red, int &s_flag,
+                                               unsigned *s_tick) {
+  const LubPlan &p = m.p[m.n - 1];
+  const unsigned bl = b - m.start[m.n - 1];  // = the slice: the tail segment has one unit
+  const int l = threadIdx.x;
+  const int rsub = l / p.PW;
+  const int col = l % p.PW;
+  const bool active = rsub < p.TR && col < p.Wv;
+  const unsigned s0 = m.tail_first - m.start[m.n - 1];  // first tail slice
+  const unsigned nslices = p.S - s0;                    // tail slices (= workgroups of the launch)
+  const unsigned ntick = nslices * m.tail_nch;
+
+  VT acc = vzero<VT>();
+  {
+    const unsigned long long rbeg = (unsigned long long)bl * p.Rs;
+    const unsigned long long rend = min(min(p.R, rbeg + p.Rs), rbeg + m.tail_rstat);
+    if (active) acc = lub_fold_range<OP, V, U, true, VT>(p, 0, col, rbeg + rsub, rend, p.TR);
+  }
+  unsigned mine = 0;
+  if (l == 0) mine = __hip_atomic_fetch_add(m.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  for (int it = 0;; ++it) {
+    // s_tick[it & 1] was last read in iteration it - 2, before the barrier of iteration it - 1,
+    // which lane 0 has passed: two slots order the broadcast with one barrier per chunk.
+    if (l == 0) s_tick[it & 1] = mine;
+    __syncthreads();
+    const unsigned t = s_tick[it & 1];
+    if (t >= ntick) {
+      if (l == 0 && t == ntick + nslices - 1)
+        __hip_atomic_store(m.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      break;
+    }
+    if (l == 0) mine = __hip_atomic_fetch_add(m.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long sbeg = (unsigned long long)(s0 + t % nslices) * p.Rs;
+    const unsigned long long rbeg = sbeg + m.tail_rstat + (unsigned long long)(t / nslices) * m.tail_rc;
+    const unsigned long long rend = min(min(p.R, sbeg + p.Rs), rbeg + m.tail_rc);
+    if (active) acc = vjoin<OP>(acc, lub_fold_range<OP, V, U, true, VT>(p, 0, col, rbeg + rsub, rend, p.TR));
+  }
+  lub_finish<OP>(p, bl, acc, red, s_flag);
+}
 
 template <Op OP, int V, int U>
 __global__ __launch_bounds__(kBlock) void lub_multi_kernel(LubMulti m) {
   using VT = typename VecOf<V>::T;
   __shared__ VT red[kBlock];
   __shared__ int s_flag;
-  const unsigned b = blockIdx.x;
-  int i = 0;
+  __shared__ unsigned s_tick[2];
+  // The body runs once per block of this workgroup, so `red` and `s_flag` are reused; every path out
+  // of the body is block-uniform (a `return` there is "next block" here) and each reuse is ordered:
+  //  - red: block_rows_combine reads red between its two __syncthreads, so the trailing one orders
+  //    its reads before the next write of red (the next combine of this block or of the next one);
+  //  - s_flag: every thread reads it after arrive_last's second __syncthreads and lane 0 writes it
+  //    again only after the first __syncthreads of the next arrive_last, which no thread passes
+  //    before it has read the previous value.
+  const unsigned total = m.start[kLubMultiMax];  // <= 2^31 - 1, so b + gridDim.x cannot wrap
+  for (unsigned b = blockIdx.x; b < total; b += gridDim.x) {
+    int i = 0;
 #pragma unroll
-  for (int j = 1; j < kLubMultiMax; ++j)
-    if (j < m.n && b >= m.start[j]) i = j;
-  lub_stream_body<OP, V, U, true, VT>(m.p[i], b - m.start[i], red, s_flag);
+    for (int j = 1; j < kLubMultiMax; ++j)
+      if (j < m.n && b >= m.start[j]) i = j;
+#ifdef LUB_STATS
+    LubStat st;
+    st.begin(blockIdx.x, i);
+#endif
+    if (m.tail_nch && b >= m.tail_first) lub_tail_block<OP, V, U, VT>(m, b, red, s_flag, s_tick);
+    else lub_stream_body<OP, V, U, true, VT>(m.p[i], b - m.start[i], red, s_flag);
+#ifdef LUB_STATS
+    st.end(m.stats, b);
+#endif
+  }
 }
 
 // self[i] := self[i] ⊔ other[i]: three streams (2 reads, 1 write), TR rows per block step.
@@ -442,6 +622,29 @@ int lattice_lub_many(crdt_ctx *ctx, Op op, const u64 *in, size_t G, size_t R, si
   return CRDT_OK;
 }
 
+// The dynamic tail of a persistent launch (lub_tail_block), where its shape allows one: the last
+// round of blocks (one per workgroup) lies in the last segment, that segment is one unit of
+// contiguous slices, and an eighth of a workgroup's share of the launch's bytes holds at least one
+// chunk of tune.lub_chunk_bytes (whole unrolled block steps of rows; 0 bytes: no tail).
+static void lub_plan_tail(const Tune &tune, LubMulti &m, int V, size_t blocks, unsigned grid, size_t bytes,
+                          unsigned *ticket) {
+  m.tail_nch = 0;
+  const LubPlan &p = m.p[m.n - 1];
+  const size_t first = blocks - grid, seg0 = m.start[m.n - 1];
+  if (tune.lub_chunk_bytes <= 0 || first < seg0 || blocks - seg0 != (size_t)p.S || p.S <= 1 || p.interleave) return;
+  const size_t row_b = (size_t)p.Wv * V * 8, step = 8 * (size_t)p.TR;
+  size_t rc = ((size_t)tune.lub_chunk_bytes + row_b - 1) / row_b;
+  rc = (rc + step - 1) / step * step;
+  size_t nch = bytes / grid / 8 / (rc * row_b);
+  if (nch * rc > p.Rs) nch = p.Rs / rc;
+  if (nch == 0 || (unsigned long long)grid * nch + grid > 0x7fffffffULL) return;
+  m.ticket = ticket;
+  m.tail_first = (unsigned)first;
+  m.tail_nch = (unsigned)nch;
+  m.tail_rc = rc;
+  m.tail_rstat = p.Rs - nch * rc;
+}
+
 // Several lattice lubs, one launch per (join op, vector width) class of up to kLubMultiMax
 // segments; results identical to one lattice_lub_many per segment (each segment's blocks run the
 // single-lub body on its own plan and scratch).
@@ -465,7 +668,7 @@ int lattice_lub_many_multi(crdt_ctx *ctx, const LubReq *reqs, size_t n) {
     }
   if (sb) {
     if (int rc = ensure_scratch(ctx, sb)) return rc;
-    if (int rc = ensure_counters(ctx, nc)) return rc;
+    if (int rc = ensure_counters(ctx, nc + n)) return rc;  // + one ticket counter per launch
   }
   {
     char *base = static_cast<char *>(ctx->scratch);
@@ -478,11 +681,12 @@ int lattice_lub_many_multi(crdt_ctx *ctx, const LubReq *reqs, size_t n) {
       }
   }
   std::vector<bool> done(n, false);
+  size_t launches = 0;
   for (size_t i = 0; i < n; ++i) {
     if (!su[i].launch || done[i]) continue;
     LubMulti m{};
     m.n = 0;
-    size_t blocks = 0;
+    size_t blocks = 0, bytes = 0;
     const Op op = reqs[i].op;
     const int V = su[i].V;
     for (size_t j = i; j < n && m.n < kLubMultiMax; ++j) {
@@ -490,21 +694,37 @@ int lattice_lub_many_multi(crdt_ctx *ctx, const LubReq *reqs, size_t n) {
       m.p[m.n] = su[j].p;
       m.start[m.n] = (unsigned)blocks;
       blocks += su[j].blocks;
+      bytes += reqs[j].G * reqs[j].R * reqs[j].W * 8;
       ++m.n;
       done[j] = true;
     }
     if (blocks > 0x7fffffffULL) return fail(ctx, CRDT_EUNSUPPORTED, "lub_many_multi: grid too large");
     for (int k = m.n; k <= kLubMultiMax; ++k) m.start[k] = (unsigned)blocks;
+#ifdef LUB_STATS
+    if (int rc = lub_stats_begin(ctx, m, blocks)) return rc;
+#endif
+    // persistent grid: one workgroup per CU (tune lubpg=N: N workgroups), never more than blocks
+    const size_t cap = ctx->tune.lub_persist_grid > 0 ? (size_t)ctx->tune.lub_persist_grid
+                                                      : (size_t)ctx->cu_count * ctx->tune.lub_blocks_per_cu;
+    const dim3 grid((unsigned)(blocks < cap ? blocks : cap));
+    if (sb) lub_plan_tail(ctx->tune, m, V, blocks, grid.x, bytes, ctx->counters + nc + launches);
+    ++launches;
     timing_begin(ctx, "lub_stream");
+#define CRDT_LAUNCH_MULTI(OPV, VV) \
+  hipLaunchKernelGGL((lub_multi_kernel<OPV, VV, 8>), grid, dim3(kBlock), 0, ctx->stream, m)
     if (op == Op::Max) {
-      if (V == 2) hipLaunchKernelGGL((lub_multi_kernel<Op::Max, 2, 8>), dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream, m);
-      else hipLaunchKernelGGL((lub_multi_kernel<Op::Max, 1, 8>), dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream, m);
+      if (V == 2) CRDT_LAUNCH_MULTI(Op::Max, 2);
+      else CRDT_LAUNCH_MULTI(Op::Max, 1);
     } else {
-      if (V == 2) hipLaunchKernelGGL((lub_multi_kernel<Op::Or, 2, 8>), dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream, m);
-      else hipLaunchKernelGGL((lub_multi_kernel<Op::Or, 1, 8>), dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream, m);
+      if (V == 2) CRDT_LAUNCH_MULTI(Op::Or, 2);
+      else CRDT_LAUNCH_MULTI(Op::Or, 1);
     }
+#undef CRDT_LAUNCH_MULTI
     timing_end(ctx);
     CRDT_HIP(ctx, hipGetLastError());
+#ifdef LUB_STATS
+    if (int rc = lub_stats_dump(ctx, m, blocks, grid.x)) return rc;
+#endif
   }
   return CRDT_OK;
 }
