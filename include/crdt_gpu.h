@@ -1267,6 +1267,106 @@ int crdt_map_nested_egress(crdt_ctx *ctx, const crdt_map_nested_states *states, 
                            const uint32_t *actors, const uint32_t *keys, const uint32_t *ikeys, uint64_t *frame_off,
                            uint8_t *bytes, size_t cap, size_t *total);
 
+/* ---- serde wire format of op streams (CmRDT ops on the wire) -----------------------------------
+ * The reference's ops derive Serialize / Deserialize like its states (orswot.rs:31-47,
+ * map.rs:50-68, mvreg.rs:38-47, vclock.rs:32-38).  These entry points turn bincode 1.x frames of
+ * op streams into the dense batches crdt_orswot_apply_batch / crdt_map_apply_batch consume, and
+ * back.  The rules above, plus: an enum = u32 variant index, then the variant's fields.
+ *   Dot<u32>                 = u32 actor, u64 counter                                  (12 B)
+ *   VClock<u32>              = u64 n, n x (u32 actor, u64 counter), actors ascending
+ *   orswot::Op<u64, u32>     = u32 0 (Add), Dot, u64 k, k x u64 member       (HashSet: any order)
+ *                            | u32 1 (Rm),  VClock, u64 k, k x u64 member
+ *   map::Op<u32, MVReg, u32> = u32 0 (Rm),  VClock, u64 k, k x u32 key       (BTreeSet: ascending)
+ *                            | u32 1 (Up),  Dot, u32 key, u32 0 (mvreg::Op::Put), VClock, u64 val
+ *   frame of state s         = Vec<Op>: u64 n_ops, then the ops back to back
+ * e.g. Vec[Add { dot: (7, 3), members: {10} }] is the 40 bytes (as 32-bit words)
+ *   1 0 | 0 | 7 3 0 | 1 0 | 10 0.
+ * The dense kind arrays keep their meaning (Orswot 0 = Add, Map 0 = Up): the Map tag is flipped on
+ * the way in and out.  Frames, dictionaries and status bits follow the state wire form: frames
+ * bytes[frame_off[s] .. frame_off[s+1]) with 4-byte-aligned offsets, sorted unique dictionaries,
+ * nothing is read past a frame.  Device pointers only.
+ *
+ * Ingest fills a crdt_*_ops_buf: the mutable twin of crdt_orswot_ops / crdt_map_ops, with the same
+ * field order and sizes and capacities where the const struct holds counts, so a filled buffer can be cast
+ * and handed to the apply call as is.  kind / actor / counter / rm_row (key, val, clk_row) hold
+ * op_cap entries, mem_off (key_off) op_cap + 1, rm_clock (clk_pool) row_cap x A, mem (keys)
+ * id_cap; row_cap <= 2^32 - 1.  Three per-state offset arrays (device, N+1, written): op_off
+ * (in the buffer: the one apply takes), row_off and id_off (the state's first clock row and first
+ * member / keyset key).  Layout: ops in frame order, states in order.  Orswot: rm_row[o] numbers
+ * the Rm clock rows in op order across the batch (0 on Adds); mem_off / mem hold every op's members
+ * in frame order, duplicates kept.  Map: clk_row[o] is one row per op (the Put clock of an Up, the
+ * rm clock of an Rm); val / key / actor / counter are 0 on Rms; key_off[o+1] = key_off[o] on Ups.
+ * Clock rows are dense [rows][A].  Every element of the first n_ops / n_rows / n_ids entries (+1
+ * for mem_off / key_off) is written by the call: nothing needs pre-zeroing.
+ * totals (host, may be NULL): non-NULL = the call synchronises once and returns {ops, rows, ids}
+ * of all well-formed frames (what the capacities must hold); with out = NULL it only sizes (status
+ * then carries bit 0 only).  NULL = no host synchronisation: capacities are checked on the device.
+ * A state whose ops, rows or ids end past a capacity gets status bit 2 and contributes no ops; its
+ * three offsets repeat the previous state's.  The cut is a suffix: every state after the first one
+ * cut gets bit 2 and no ops as well, an empty or small one that would have fit included (its ops
+ * end past the same capacity in the uncut layout), so the states kept are always a prefix of the
+ * batch, laid out exactly as a call with enough room lays them out.  Nothing is written past a
+ * capacity.  Bounds to size by without a sync, B_s = bytes of frame s:
+ * ops <= (B_s - 8) / 20 (the smallest op, an Rm with an empty clock and set, is 4 + 8 + 8 bytes),
+ * rows <= ops, ids <= B_s / 8 (Orswot) or B_s / 4 (Map).
+ * status[s] (device u32, written for every s): bit 0 = malformed (truncated, trailing bytes,
+ * misaligned offset, a count that cannot fit the bytes left, an unknown variant tag, a Map Up whose
+ * MVReg tag is not 0): the frame contributes no ops at all and shifts no neighbour's offsets;
+ * bit 1 = an id missing from its dictionary: in a clock record the record is skipped, as a dot's
+ * actor, an Up's key or a set's member / key it is written as 0xFFFFFFFF (the apply kernels skip
+ * and report that in their bit 1; the op keeps its place); bit 2 = capacity.
+ * Egress writes the frames of N states' op streams with the sizing protocol of crdt_orswot_egress
+ * (*total always; the bytes when `bytes` is non-NULL and cap >= *total).  status[s] (device u32,
+ * written): bit 1 = the state has an op with no wire form (a kind other than 0 / 1, an index >= A /
+ * M / K, a row >= its pool, an id range reversed or ending past n_mem / n_keys, an invalid op_off);
+ * its frame is the empty Vec (u64 0).  Clock rows are written as their non-zero actors ascending,
+ * id lists in list order, so ingest -> egress reproduces byte for byte any well-formed frame whose
+ * ids are all in the dictionaries.  Limits: none on A, M, K (dictionaries that do not fit beside the
+ * frame ring in 64 KiB of LDS are searched in global memory). */
+typedef struct crdt_orswot_ops_buf {
+  size_t op_cap;
+  uint64_t *op_off;   /* [N+1]        */
+  uint8_t *kind;      /* [op_cap]     */
+  uint32_t *actor;    /* [op_cap]     */
+  uint64_t *counter;  /* [op_cap]     */
+  uint32_t *rm_row;   /* [op_cap]     */
+  uint64_t *rm_clock; /* [row_cap][A] */
+  size_t row_cap;
+  uint64_t *mem_off;  /* [op_cap+1]   */
+  uint32_t *mem;      /* [id_cap]     */
+  size_t id_cap;
+} crdt_orswot_ops_buf;
+
+typedef struct crdt_map_ops_buf {
+  size_t op_cap;
+  uint64_t *op_off;   /* [N+1]        */
+  uint8_t *kind;      /* [op_cap]     */
+  uint32_t *actor;    /* [op_cap]     */
+  uint64_t *counter;  /* [op_cap]     */
+  uint32_t *key;      /* [op_cap]     */
+  uint64_t *val;      /* [op_cap]     */
+  uint32_t *clk_row;  /* [op_cap]     */
+  uint64_t *clk_pool; /* [row_cap][A] */
+  size_t row_cap;
+  uint64_t *key_off;  /* [op_cap+1]   */
+  uint32_t *keys;     /* [id_cap]     */
+  size_t id_cap;
+} crdt_map_ops_buf;
+
+int crdt_orswot_ops_ingest(crdt_ctx *ctx, const uint8_t *bytes, const uint64_t *frame_off, size_t N,
+                           const uint32_t *actors, size_t A, const uint64_t *members, size_t M,
+                           const crdt_orswot_ops_buf *out, uint64_t *row_off, uint64_t *id_off, uint32_t *status,
+                           uint64_t *totals);
+int crdt_map_ops_ingest(crdt_ctx *ctx, const uint8_t *bytes, const uint64_t *frame_off, size_t N,
+                        const uint32_t *actors, size_t A, const uint32_t *keys, size_t K, const crdt_map_ops_buf *out,
+                        uint64_t *row_off, uint64_t *id_off, uint32_t *status, uint64_t *totals);
+int crdt_orswot_ops_egress(crdt_ctx *ctx, const crdt_orswot_ops *ops, size_t N, const uint32_t *actors, size_t A,
+                           const uint64_t *members, size_t M, uint64_t *frame_off, uint8_t *bytes, size_t cap,
+                           size_t *total, uint32_t *status);
+int crdt_map_ops_egress(crdt_ctx *ctx, const crdt_map_ops *ops, size_t N, const uint32_t *actors, size_t A,
+                        const uint32_t *keys, size_t K, uint64_t *frame_off, uint8_t *bytes, size_t cap, size_t *total,
+                        uint32_t *status);
+
 /* ---- synthetic inputs (bench / test data, generated in HBM) --------------------------------
  * Counter-based and reproducible on the CPU (oracle/oracle.py synth_* restates them; small
  * fixtures of both are pinned by tests/golden/make_golden.py -> tests/golden/synth.json).

@@ -63,6 +63,7 @@ EXPORTS = (
     "crdt_map_counter_ingest", "crdt_map_counter_egress", "crdt_map_orswot_ingest", "crdt_map_orswot_egress",
     "crdt_orswot_read", "crdt_orswot_contains", "crdt_mvreg_read", "crdt_map_read", "crdt_map_get",
     "crdt_vclock_derive_add",
+    "crdt_orswot_ops_ingest", "crdt_map_ops_ingest", "crdt_orswot_ops_egress", "crdt_map_ops_egress",
 )
 
 
@@ -158,6 +159,19 @@ class MapOps(ctypes.Structure):  # crdt_map_ops
     _fields_ = [("n_ops", S), ("op_off", P), ("kind", P), ("actor", P), ("counter", P), ("key", P), ("val", P),
                 ("clk_row", P), ("clk_pool", P), ("n_clk_rows", S), ("key_off", P), ("keys", P),
                 ("n_keys", S)]
+
+
+class OrswotOpsBuf(ctypes.Structure):  # crdt_orswot_ops_buf: OrswotOps with capacities for counts
+    _fields_ = [
+        ("op_cap", S), ("op_off", P), ("kind", P), ("actor", P), ("counter", P), ("rm_row", P),
+        ("rm_clock", P), ("row_cap", S), ("mem_off", P), ("mem", P), ("id_cap", S),
+    ]
+
+
+class MapOpsBuf(ctypes.Structure):  # crdt_map_ops_buf: MapOps with capacities for counts
+    _fields_ = [("op_cap", S), ("op_off", P), ("kind", P), ("actor", P), ("counter", P), ("key", P), ("val", P),
+                ("clk_row", P), ("clk_pool", P), ("row_cap", S), ("key_off", P), ("keys", P),
+                ("id_cap", S)]
 
 
 class MapDeferred(ctypes.Structure):  # crdt_map_deferred
@@ -377,6 +391,15 @@ _SIGS.update({  # batched ReadCtx queries (csrc/read.hip)
     "crdt_mvreg_read": ([P, ctypes.POINTER(MVRegStates), P, S, P, P], ctypes.c_int),
     "crdt_map_get": ([P, ctypes.POINTER(MapStates), P, P, S, P, P, P, P, P, P, P], ctypes.c_int),
     "crdt_vclock_derive_add": ([P, P, S, S, S, P, P, S, P, P], ctypes.c_int),
+})
+_SIGS.update({  # op streams on the wire (csrc/wire_ops.hip)
+    "crdt_orswot_ops_ingest": ([P, P, P, S, P, S, P, S, ctypes.POINTER(OrswotOpsBuf), P, P, P,
+                                ctypes.POINTER(U64)], ctypes.c_int),
+    "crdt_map_ops_ingest": ([P, P, P, S, P, S, P, S, ctypes.POINTER(MapOpsBuf), P, P, P, ctypes.POINTER(U64)],
+                            ctypes.c_int),
+    "crdt_orswot_ops_egress": ([P, ctypes.POINTER(OrswotOps), S, P, S, P, S, P, P, S, ctypes.POINTER(S), P],
+                               ctypes.c_int),
+    "crdt_map_ops_egress": ([P, ctypes.POINTER(MapOps), S, P, S, P, S, P, P, S, ctypes.POINTER(S), P], ctypes.c_int),
 })
 for _t in ("vclock", "gcounter", "pncounter", "gset"):
     _SIGS[f"crdt_{_t}_lub_many_sharded"] = ([P, P, S, S, S, S, S, P], ctypes.c_int)

@@ -9,6 +9,11 @@ holding u64 ids).  Nothing here runs on the host except the shape checks.
 
     rows, status = vclock_ingest(bytes, frame_off, actors)          # (N, A), (N,) int32
     frame_off, data = vclock_egress(rows, actors)                   # (N+1,), (total,) uint8
+
+Op streams travel the same way (one Vec<Op> frame per state, Orswot<u64, u32> and
+Map<u32, MVReg<u64, u32>, u32>): orswot_ops_ingest / map_ops_ingest return the OrswotOpBatch /
+MapOpBatch that orswot.apply_batch / map.apply_batch take, orswot_ops_egress / map_ops_egress write
+such a batch as frames.
 """
 from __future__ import annotations
 
@@ -17,6 +22,7 @@ from typing import NamedTuple, Optional
 
 import torch
 
+from . import _abi
 from .context import Context, dptr
 
 BAD, MISSING, CAP = 1, 2, 4  # status bits
@@ -448,3 +454,187 @@ def map_nested_egress(states: MapNestedFrames, actors: torch.Tensor, keys: torch
     s, d = _nested_struct(ctx, states, "wire.map_nested_egress")
     return _egress(ctx, "crdt_map_nested_egress", states.clock.shape[0], states.clock.device, ctypes.byref(s),
                    ctypes.byref(d), dptr(actors), dptr(keys), dptr(ikeys))
+
+
+# ---- op streams on the wire (include/crdt_gpu.h "serde wire format of op streams") ------------------
+class OpsIngest(NamedTuple):
+    """Result of orswot_ops_ingest / map_ops_ingest."""
+    ops: tuple                # orswot.OrswotOpBatch / map.MapOpBatch: goes to apply_batch unchanged
+    status: torch.Tensor      # (N,) int32: BAD / MISSING / CAP bits
+    row_off: torch.Tensor     # (N+1,) int64: the state's first clock row
+    id_off: torch.Tensor      # (N+1,) int64: the state's first member / keyset key
+    totals: Optional[tuple]   # (ops, rows, ids) of the well-formed frames; None with sync=False
+
+
+_I32 = (torch.int32, torch.uint32)
+_I64 = (torch.int64, torch.uint64)
+
+
+def _ops_check(what: str, tensors) -> None:
+    """ValueError checks, all before any library call (and before a Context exists): every
+    (tensor, name, dtypes) is a contiguous cuda tensor of one of `dtypes`, all on one device."""
+    dev = None
+    for t, nm, dts in tensors:  # dtypes and layouts of every argument first, then the device
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{what}({nm}): expected a torch.Tensor")
+        if t.dtype not in dts:
+            raise ValueError(f"{what}({nm}): dtype {t.dtype}; expected one of {dts}")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}({nm}): must be contiguous")
+    for t, nm, dts in tensors:
+        if t.device.type != "cuda":
+            raise ValueError(f"{what}({nm}): tensor on {t.device}; expected a cuda tensor")
+        dev = t.device if dev is None else dev
+        if t.device != dev:
+            raise ValueError(f"{what}({nm}): tensor on {t.device}; the others are on {dev}")
+
+
+def _ops_frames(what, data, frame_off, actors, ids, id_dt, id_nm):
+    _ops_check(what, ((data, "bytes", (torch.uint8,)), (frame_off, "frame_off", (torch.int64,)),
+                      (actors, "actors", (torch.int32,)), (ids, id_nm, (id_dt,))))
+    if data.dim() != 1 or frame_off.dim() != 1 or frame_off.shape[0] < 1:
+        raise ValueError(f"{what}: bytes must be a uint8 vector and frame_off an int64 (N+1,) tensor")
+    if actors.dim() != 1 or ids.dim() != 1 or actors.shape[0] == 0 or ids.shape[0] == 0:
+        raise ValueError(f"{what}: the dictionaries must be non-empty vectors")
+    return frame_off.shape[0] - 1, actors.shape[0], ids.shape[0]
+
+
+def _ops_caps(what, sync, caps):
+    if sync:
+        if caps is not None:
+            raise ValueError(f"{what}: capacities are chosen by the sizing call unless sync=False")
+        return None
+    if caps is None or len(caps) != 3 or any(int(c) < 0 for c in caps):
+        raise ValueError(f"{what}: sync=False needs caps=(op_cap, row_cap, id_cap)")
+    return tuple(int(c) for c in caps)
+
+
+def _ops_ingest(what, fn, buf_cls, is_map, data, frame_off, actors, ids, N, A, sync, caps, ctx):
+    from .map import MapOpBatch
+    from .orswot import OrswotOpBatch
+    ctx = _ctx(data, ctx)
+    dev = data.device
+    U = ids.shape[0]
+    status = torch.empty(N, dtype=torch.int32, device=dev)
+    row_off = torch.empty(N + 1, dtype=torch.int64, device=dev)
+    id_off = torch.empty(N + 1, dtype=torch.int64, device=dev)
+    op_off = torch.empty(N + 1, dtype=torch.int64, device=dev)
+    head = (_ptr_or_dummy(data), dptr(frame_off), N, dptr(actors), A, dptr(ids), U)
+    totals = None
+    if sync:  # size, then fill with exactly enough room (+ one pad row / id, as encode_ops leaves)
+        tot = (ctypes.c_uint64 * 3)()
+        if N:
+            ctx.call(fn, *head, None, None, None, dptr(status), tot)
+        totals = (int(tot[0]), int(tot[1]), int(tot[2]))
+        caps = totals
+    n_op, n_row, n_id = caps
+    e = lambda n, dt: torch.empty(n, dtype=dt, device=dev)  # noqa: E731
+    kind, actor, counter, row = e(n_op, torch.uint8), e(n_op, torch.int32), e(n_op, torch.int64), e(n_op, torch.int32)
+    pool = torch.empty((n_row + 1, A), dtype=torch.int64, device=dev)
+    ids_off, idv = e(n_op + 1, torch.int64), e(n_id + 1, torch.int32)
+    pool[n_row].zero_()
+    idv[n_id].zero_()
+    b = buf_cls()
+    b.op_cap, b.row_cap, b.id_cap = n_op, n_row, n_id
+    b.op_off, b.kind, b.actor, b.counter = dptr(op_off), dptr(kind), dptr(actor), dptr(counter)
+    if is_map:
+        key, val = e(n_op, torch.int32), e(n_op, torch.int64)
+        b.key, b.val, b.clk_row, b.clk_pool, b.key_off, b.keys = (dptr(key), dptr(val), dptr(row), dptr(pool),
+                                                                  dptr(ids_off), dptr(idv))
+        ops = MapOpBatch(op_off, kind, actor, counter, key, val, row, pool, ids_off, idv)
+    else:
+        b.rm_row, b.rm_clock, b.mem_off, b.mem = dptr(row), dptr(pool), dptr(ids_off), dptr(idv)
+        ops = OrswotOpBatch(op_off, kind, actor, counter, row, pool, ids_off, idv)
+    if N:
+        ctx.call(fn, *head, ctypes.byref(b), dptr(row_off), dptr(id_off), dptr(status), None)
+    else:
+        for t in (op_off, row_off, id_off, ids_off[:1]):
+            t.zero_()
+    return OpsIngest(ops, status, row_off, id_off, totals)
+
+
+def orswot_ops_ingest(data: torch.Tensor, frame_off: torch.Tensor, actors: torch.Tensor, members: torch.Tensor,
+                      sync: bool = True, caps=None, ctx: Optional[Context] = None) -> OpsIngest:
+    """Frames of Vec<orswot::Op<u64, u32>> (one per state) -> OpsIngest with an orswot.OrswotOpBatch.
+    sync=True sizes first (one host synchronisation) and allocates exactly; sync=False takes
+    caps=(op_cap, row_cap, id_cap), never synchronises, and marks states past a capacity with CAP."""
+    what = "wire.orswot_ops_ingest"
+    caps = _ops_caps(what, sync, caps)
+    N, A, _ = _ops_frames(what, data, frame_off, actors, members, torch.int64, "members")
+    return _ops_ingest(what, "crdt_orswot_ops_ingest", _abi.OrswotOpsBuf, False, data, frame_off, actors,
+                       members, N, A, sync, caps, ctx)
+
+
+def map_ops_ingest(data: torch.Tensor, frame_off: torch.Tensor, actors: torch.Tensor, keys: torch.Tensor,
+                   sync: bool = True, caps=None, ctx: Optional[Context] = None) -> OpsIngest:
+    """Frames of Vec<map::Op<u32, MVReg<u64, u32>, u32>> -> OpsIngest with a map.MapOpBatch (see
+    orswot_ops_ingest for sync / caps; id_cap counts keyset keys)."""
+    what = "wire.map_ops_ingest"
+    caps = _ops_caps(what, sync, caps)
+    N, A, _ = _ops_frames(what, data, frame_off, actors, keys, torch.int32, "keys")
+    return _ops_ingest(what, "crdt_map_ops_ingest", _abi.MapOpsBuf, True, data, frame_off, actors, keys, N, A,
+                       sync, caps, ctx)
+
+
+def _ops_egress(what, fn, o, ops, N, actors, ids, ctx):
+    ctx = _ctx(ops.op_off, ctx)
+    dev = ops.op_off.device
+    status = torch.empty(N, dtype=torch.int32, device=dev)
+    args = (ctypes.byref(o), N, dptr(actors), actors.shape[0], dptr(ids), ids.shape[0])
+    frame_off = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+    total = ctypes.c_size_t()
+    ctx.call(fn, *args, dptr(frame_off), None, 0, ctypes.byref(total), dptr(status))
+    data = torch.empty(max(total.value, 1), dtype=torch.uint8, device=dev)
+    ctx.call(fn, *args, dptr(frame_off), dptr(data), data.numel(), ctypes.byref(total), dptr(status))
+    return frame_off, data[:total.value], status
+
+
+def _ops_batch_check(what, ops, fields, actors, ids, id_dt, id_nm, pool_nm):
+    if not hasattr(ops, "_fields") or tuple(ops._fields) != fields:
+        raise ValueError(f"{what}: expected an op batch with fields {fields}")
+    want = {"op_off": _I64, "kind": (torch.uint8,), "counter": _I64, "val": _I64, pool_nm: _I64, "mem_off": _I64,
+            "key_off": _I64}
+    _ops_check(what, [(t, nm, want.get(nm, _I32)) for nm, t in zip(ops._fields, ops)]
+               + [(actors, "actors", (torch.int32,)), (ids, id_nm, (id_dt,))])
+    n = ops.kind.shape[0]
+    pool = getattr(ops, pool_nm)
+    if ops.op_off.dim() != 1 or ops.op_off.shape[0] < 1 or pool.dim() != 2 or pool.shape[1] != actors.shape[0]:
+        raise ValueError(f"{what}: op_off (N+1,) and {pool_nm} (rows, A) expected")
+    if actors.dim() != 1 or ids.dim() != 1 or actors.shape[0] == 0 or ids.shape[0] == 0:
+        raise ValueError(f"{what}: the dictionaries must be non-empty vectors")
+    for nm, t in zip(ops._fields, ops):
+        if nm in ("mem_off", "key_off"):
+            if t.dim() != 1 or t.shape[0] < n + 1:
+                raise ValueError(f"{what}: {nm} needs n_ops+1 entries")
+        elif nm not in ("op_off", pool_nm, "mem", "keys") and tuple(t.shape) != (n,):
+            raise ValueError(f"{what}: ops.{nm} must have n_ops entries")
+    return ops.op_off.shape[0] - 1, n
+
+
+def orswot_ops_egress(ops, actors: torch.Tensor, members: torch.Tensor, ctx: Optional[Context] = None):
+    """orswot.OrswotOpBatch -> (frame_off (N+1,), bytes, status (N,) int32): one Vec<orswot::Op> frame
+    per state.  status bit 1 (MISSING): the state had an op with no wire form and its frame is the
+    empty Vec."""
+    from .orswot import OrswotOpBatch
+    what = "wire.orswot_ops_egress"
+    N, n = _ops_batch_check(what, ops, OrswotOpBatch._fields, actors, members, torch.int64, "members", "rm_clock")
+    o = _abi.OrswotOps()
+    o.n_ops = n
+    o.op_off, o.kind, o.actor, o.counter = dptr(ops.op_off), dptr(ops.kind), dptr(ops.actor), dptr(ops.counter)
+    o.rm_row, o.rm_clock, o.n_rm_rows = dptr(ops.rm_row), dptr(ops.rm_clock), ops.rm_clock.shape[0]
+    o.mem_off, o.mem, o.n_mem = dptr(ops.mem_off), dptr(ops.mem), ops.mem.shape[0]
+    return _ops_egress(what, "crdt_orswot_ops_egress", o, ops, N, actors, members, ctx)
+
+
+def map_ops_egress(ops, actors: torch.Tensor, keys: torch.Tensor, ctx: Optional[Context] = None):
+    """map.MapOpBatch -> (frame_off (N+1,), bytes, status (N,) int32): one Vec<map::Op> frame per
+    state (keysets in list order: ascending indices give the BTreeSet's order)."""
+    from .map import MapOpBatch
+    what = "wire.map_ops_egress"
+    N, n = _ops_batch_check(what, ops, MapOpBatch._fields, actors, keys, torch.int32, "keys_dict", "clk_pool")
+    o = _abi.MapOps()
+    o.n_ops = n
+    o.op_off, o.kind, o.actor, o.counter = dptr(ops.op_off), dptr(ops.kind), dptr(ops.actor), dptr(ops.counter)
+    o.key, o.val, o.clk_row, o.clk_pool = dptr(ops.key), dptr(ops.val), dptr(ops.clk_row), dptr(ops.clk_pool)
+    o.n_clk_rows, o.key_off, o.keys, o.n_keys = ops.clk_pool.shape[0], dptr(ops.key_off), dptr(ops.keys), ops.keys.shape[0]
+    return _ops_egress(what, "crdt_map_ops_egress", o, ops, N, actors, keys, ctx)

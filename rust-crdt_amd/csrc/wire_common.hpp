@@ -1,5 +1,5 @@
 // Shared pieces of the serde wire kernels (wire.hip: the reference types and Map<K, MVReg>;
-// wire_vmap.hip: the value-typed Maps): frame access, dictionary lookups, VClock parse / write.
+// wire_vmap.hip: the value-typed Maps; wire_ops.hip: op streams): frame access, dictionary lookups, VClock parse / write.
 // The encoding (bincode 1.x, default options) is restated at the top of wire.hip.
 #pragma once
 #include "common.hpp"
@@ -118,6 +118,96 @@ __device__ inline unsigned long long write_vclock(uint32_t *w, unsigned long lon
   }
   return k + 2 + 3 * n;
 }
+
+// ---- the walk's frame reader (wire.hip "walk + batched parse"; wire_ops.hip) ----------------------
+// The frame streams through a per-wave LDS ring of RING windows by LDS-DMA, issued RING windows
+// ahead of the walk; the current window sits in four registers per lane, so a word the walk reads
+// costs a readlane, not a memory round trip.
+constexpr int kWalkWin = 256;  // words per window (one per lane per register, 4 registers)
+constexpr int kWalkRing = 8;   // LDS ring windows per wave
+
+template <int N>
+__device__ __forceinline__ void wire_vmcnt() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+// A wave-uniform 64-bit value the compiler cannot prove uniform (the walk's positions): made so, so
+// that the walk's arithmetic and branches stay scalar instead of EXEC-masked vector code.
+__device__ __forceinline__ unsigned long long uni64(unsigned long long x) {
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)x), hi = __builtin_amdgcn_readfirstlane((unsigned)(x >> 32));
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+template <int RING = kWalkRing>
+struct MapWalk {
+  const uint32_t *fw;
+  unsigned long long nw, nwin, issued, cur;
+  uint32_t *ring;
+  uint32_t r0, r1, r2, r3;
+
+  __device__ void dma(unsigned long long wi, int lane) {
+    uint32_t *dst = ring + (wi % RING) * kWalkWin;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const unsigned long long w = wi * kWalkWin + 64 * j + lane;
+      __builtin_amdgcn_global_load_lds(fw + (w < nw ? w : nw - 1),
+                                       (__attribute__((address_space(3))) void *)(dst + 64 * j), 4, 0, 0);
+    }
+  }
+  __device__ void start(int lane) {
+    nw = uni64(nw);
+    nwin = uni64(nwin);
+    issued = 0;
+    cur = ~0ull;
+    while (issued < nwin && issued < (unsigned long long)RING) {
+      dma(issued, lane);
+      issued = uni64(issued + 1);
+    }
+  }
+  // window wi into registers (wi > cur); then keep the ring full
+  __device__ void load(unsigned long long wi, int lane) {
+    // windows issued after wi: every vector-memory op issued since wi's DMA counts too, so this
+    // waits at least for wi (in-order counter)
+    switch ((int)(issued - 1 - wi)) {
+      case 0: wire_vmcnt<0>(); break;
+      case 1: wire_vmcnt<4>(); break;
+      case 2: wire_vmcnt<8>(); break;
+      case 3: wire_vmcnt<12>(); break;
+      case 4: wire_vmcnt<16>(); break;
+      case 5: wire_vmcnt<20>(); break;
+      case 6: wire_vmcnt<24>(); break;
+      default: wire_vmcnt<28>(); break;
+    }
+    const uint32_t *src = ring + (wi % RING) * kWalkWin + lane;
+    r0 = src[0];
+    r1 = src[64];
+    r2 = src[128];
+    r3 = src[192];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the slot is read: it may be refilled
+    cur = uni64(wi);
+    while (issued < nwin && issued <= wi + RING) {
+      dma(issued, lane);
+      issued = uni64(issued + 1);
+    }
+  }
+  __device__ uint32_t get(unsigned long long k, int lane) {
+    k = uni64(k);
+    const unsigned long long wi = k / kWalkWin;
+    if (wi != uni64(cur)) load(wi, lane);
+    const int off = (int)(k % kWalkWin), l = off & 63, q = off >> 6;
+    // four readlanes and scalar selects: a switch over r0..r3 may be lowered as an indexed access
+    // to a stack copy of them (scratch: a memory round trip per word read)
+    const uint32_t a = __builtin_amdgcn_readlane(r0, l), b = __builtin_amdgcn_readlane(r1, l);
+    const uint32_t c = __builtin_amdgcn_readlane(r2, l), d = __builtin_amdgcn_readlane(r3, l);
+    return q == 0 ? a : (q == 1 ? b : (q == 2 ? c : d));
+  }
+  __device__ u64 get64(unsigned long long k, int lane) { return (u64)get(k, lane) | ((u64)get(k + 1, lane) << 32); }
+};
+
+// out[0..n] = exclusive scan of in[0..n), out[n] = sum (wire.hip's scan kernels).  host_total
+// non-NULL: the sum is copied back (synchronises).  scratch: ceil(n / kScanItems) + 2 u64.
+int exclusive_scan(crdt_ctx *ctx, const u64 *in, u64 *out, unsigned long long n, u64 *scratch,
+                   unsigned long long *host_total);
 
 inline unsigned wave_grid(crdt_ctx *ctx, unsigned long long waves, int wpb, int per_cu) {
   const unsigned long long want = (waves + wpb - 1) / wpb;
