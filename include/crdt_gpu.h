@@ -1367,6 +1367,138 @@ int crdt_map_ops_egress(crdt_ctx *ctx, const crdt_map_ops *ops, size_t N, const 
                         const uint32_t *keys, size_t K, uint64_t *frame_off, uint8_t *bytes, size_t cap, size_t *total,
                         uint32_t *status);
 
+/* ---- serde wire format of the value-typed Maps' op streams -------------------------------------
+ * Frames of Vec<map::Op<u32, V, u32>> for V = GCounter<u32>, PNCounter<u32>, Orswot<u64, u32> and
+ * Map<u32, MVReg<u64, u32>, u32> (map.rs:50-68 with gcounter.rs:37, pncounter.rs:35-51,
+ * orswot.rs:31-47, mvreg.rs:38-47 inside) <-> the dense batches of crdt_map_counter_apply_batch /
+ * crdt_map_orswot_apply_batch / crdt_map_nested_apply_batch.  The rules above; in 32-bit words:
+ *   Op::Rm (every V)   = 0, VClock, u64 k, k x u32 key              (BTreeSet: ascending)  5 + 3n + k
+ *   Op::Up, GCounter   = 1, Dot, u32 key, Dot                                                8
+ *   Op::Up, PNCounter  = 1, Dot, u32 key, Dot, u32 dir (0 Pos, 1 Neg)                        9
+ *   Op::Up, Orswot     = 1, Dot, u32 key, 0 (Add), Dot, u64 k, k x u64 member                11 + 2k
+ *                      | 1, Dot, u32 key, 1 (Rm), VClock, u64 k, k x u64 member              10 + 3n + 2k
+ *   Op::Up, Map<MVReg> = 1, Dot, u32 key, 0 (inner Rm), VClock, u64 k, k x u32 ikey          10 + 3n + k
+ *                      | 1, Dot, u32 key, 1 (inner Up), Dot, u32 ikey, 0 (Put), VClock, u64 val  15 + 3n
+ *   frame of state s   = u64 n_ops, then the ops back to back
+ * e.g. Vec[Up { dot: (7, 3), key: 5, op: Dot (7, 2) }] of a Map<u32, GCounter> is the 40 bytes
+ *   1 0 | 1 | 7 3 0 | 5 | 7 2 0.
+ * The dense kind (0 = Up, 1 = Rm) and ikind (0 = inner Up, 1 = inner Rm) keep the apply structs'
+ * meaning: both wire tags are flipped on the way in and out; vkind (0 = Add, 1 = Rm) and vdir match
+ * the wire.  Frames, dictionaries (idict: the sorted u32 inner-key dictionary, K2 <= 256, else
+ * CRDT_EUNSUPPORTED before any launch), alignment and device-pointers-only as for crdt_map_ops_ingest.
+ *
+ * Ingest fills a crdt_map_*_ops_buf, the mutable twin of the const struct (same field order and
+ * sizes, capacities where it holds counts), laid out as the host encoders of crdts_gpu/map.py lay a
+ * batch out.  Counter Maps: clk_row numbers one pool row per Map Rm in op order across the batch, 0
+ * on Ups; the Up-only fields are 0 on Rms; key_off[o+1] = key_off[o] on Ups; pn = 0 reads GCounter
+ * frames (vdir written 0), pn = 1 PNCounter frames.  Orswot Map: one pool row per Orswot Rm and per
+ * Map Rm, none for an Add (clk_row 0); mem_off / mems hold every Up's members in frame order,
+ * duplicates kept; key_off / keys the Map Rm keysets.  Nested Map: one pool row per op (the Put
+ * clock, the inner rm clock or the outer rm clock); an inner Rm's keyset becomes the mask ikeys
+ * [op_cap][K2w] (K2w = 1 up to K2 = 64, else ceil(K2 / 64)), zero on every other op.  Every element
+ * the counts cover is written: nothing needs pre-zeroing.  Per-state offsets (device, N+1, written):
+ * op_off, row_off, key_first (the state's first keyset key) and, for the Orswot Map, mem_first.
+ * totals (host, may be NULL) = {ops, rows, keys, mems} of the well-formed frames, four words for
+ * all three types (mems = 0 where there is no member pool).  The sizing call (out = NULL), the
+ * no-sync path (totals = NULL) and the suffix cut are those of crdt_map_ops_ingest, over three
+ * (Orswot Map: four) capacities: the first state over any capacity and every state after it get
+ * bit 2 and no ops, the states kept are a prefix laid out as an uncut call lays them out, nothing
+ * is written past a capacity.  No-sync bounds, B_s = bytes of frame s: ops <= (B_s - 8) / 20 (the
+ * smallest op is still the 20-byte Rm), rows <= ops, keys <= B_s / 4, mems <= B_s / 8.
+ * status[s] (written for every s): bit 0 = malformed (as crdt_map_ops_ingest, plus an unknown value
+ * tag, a PNCounter dir > 1, an inner Up whose MVReg tag is not 0): no ops, no neighbour's offsets
+ * shifted; bit 1 = an id missing from its dictionary: a clock record is skipped; a dot's actor, an
+ * Up's key, a member, a keyset key or an inner Up's ikey is written as 0xFFFFFFFF (the apply kernels
+ * skip and report these); a missing inner-Rm key is left out of the mask; bit 2 = capacity.
+ * Egress: the sizing protocol of crdt_map_ops_egress.  status[s] bit 1 = the state has an op with no
+ * wire form (a kind / vkind / ikind / vdir other than 0 or 1, vdir = 1 with pn = 0, an index >= A /
+ * K / M / K2 or a mask bit >= K2, a row >= its pool, an id range reversed or past its pool, a Map Rm
+ * while key_off is NULL, an invalid op_off); its frame is the empty Vec.  vdir = NULL: all P.  Clock
+ * rows are written as their non-zero actors ascending, id lists in list order, mask bits ascending,
+ * so ingest -> egress reproduces byte for byte any well-formed frame whose ids are all in the
+ * dictionaries. */
+typedef struct crdt_map_counter_ops_buf {
+  size_t op_cap;
+  uint64_t *op_off;    /* [N+1]        */
+  uint8_t *kind;       /* [op_cap]     */
+  uint32_t *actor;     /* [op_cap]     */
+  uint64_t *counter;   /* [op_cap]     */
+  uint32_t *key;       /* [op_cap]     */
+  uint32_t *vactor;    /* [op_cap]     */
+  uint64_t *vcounter;  /* [op_cap]     */
+  uint8_t *vdir;       /* [op_cap]     */
+  uint32_t *clk_row;   /* [op_cap]     */
+  uint64_t *clk_pool;  /* [row_cap][A] */
+  size_t row_cap;
+  uint64_t *key_off;   /* [op_cap+1]   */
+  uint32_t *keys;      /* [key_cap]    */
+  size_t key_cap;
+} crdt_map_counter_ops_buf;
+
+typedef struct crdt_map_orswot_ops_buf {
+  size_t op_cap;
+  uint64_t *op_off;    /* [N+1]        */
+  uint8_t *kind;       /* [op_cap]     */
+  uint32_t *actor;     /* [op_cap]     */
+  uint64_t *counter;   /* [op_cap]     */
+  uint32_t *key;       /* [op_cap]     */
+  uint8_t *vkind;      /* [op_cap]     */
+  uint32_t *vactor;    /* [op_cap]     */
+  uint64_t *vcounter;  /* [op_cap]     */
+  uint32_t *clk_row;   /* [op_cap]     */
+  uint64_t *clk_pool;  /* [row_cap][A] */
+  size_t row_cap;
+  uint64_t *key_off;   /* [op_cap+1]   */
+  uint32_t *keys;      /* [key_cap]    */
+  size_t key_cap;
+  uint64_t *mem_off;   /* [op_cap+1]   */
+  uint32_t *mems;      /* [mem_cap]    */
+  size_t mem_cap;
+} crdt_map_orswot_ops_buf;
+
+typedef struct crdt_map_nested_ops_buf {
+  size_t op_cap;
+  uint64_t *op_off;    /* [N+1]        */
+  uint8_t *kind;       /* [op_cap]     */
+  uint32_t *actor;     /* [op_cap]     */
+  uint64_t *counter;   /* [op_cap]     */
+  uint32_t *key;       /* [op_cap]     */
+  uint8_t *ikind;      /* [op_cap]     */
+  uint32_t *iactor;    /* [op_cap]     */
+  uint64_t *icounter;  /* [op_cap]     */
+  uint32_t *ikey;      /* [op_cap]     */
+  uint64_t *val;       /* [op_cap]     */
+  uint64_t *ikeys;     /* [op_cap][K2w] */
+  uint32_t *clk_row;   /* [op_cap]     */
+  uint64_t *clk_pool;  /* [row_cap][A] */
+  size_t row_cap;
+  uint64_t *key_off;   /* [op_cap+1]   */
+  uint32_t *keys;      /* [key_cap]    */
+  size_t key_cap;
+} crdt_map_nested_ops_buf;
+
+int crdt_map_counter_ops_ingest(crdt_ctx *ctx, const uint8_t *bytes, const uint64_t *frame_off, size_t N,
+                                const uint32_t *actors, size_t A, const uint32_t *keys, size_t K, int pn,
+                                const crdt_map_counter_ops_buf *out, uint64_t *row_off, uint64_t *key_first,
+                                uint32_t *status, uint64_t *totals);
+int crdt_map_orswot_ops_ingest(crdt_ctx *ctx, const uint8_t *bytes, const uint64_t *frame_off, size_t N,
+                               const uint32_t *actors, size_t A, const uint32_t *keys, size_t K, const uint64_t *members,
+                               size_t M, const crdt_map_orswot_ops_buf *out, uint64_t *row_off, uint64_t *key_first,
+                               uint64_t *mem_first, uint32_t *status, uint64_t *totals);
+int crdt_map_nested_ops_ingest(crdt_ctx *ctx, const uint8_t *bytes, const uint64_t *frame_off, size_t N,
+                               const uint32_t *actors, size_t A, const uint32_t *keys, size_t K, const uint32_t *idict,
+                               size_t K2, const crdt_map_nested_ops_buf *out, uint64_t *row_off, uint64_t *key_first,
+                               uint32_t *status, uint64_t *totals);
+int crdt_map_counter_ops_egress(crdt_ctx *ctx, const crdt_map_counter_ops *ops, size_t N, const uint32_t *actors, size_t A,
+                                const uint32_t *keys, size_t K, int pn, uint64_t *frame_off, uint8_t *bytes, size_t cap,
+                                size_t *total, uint32_t *status);
+int crdt_map_orswot_ops_egress(crdt_ctx *ctx, const crdt_map_orswot_ops *ops, size_t N, const uint32_t *actors, size_t A,
+                               const uint32_t *keys, size_t K, const uint64_t *members, size_t M, uint64_t *frame_off,
+                               uint8_t *bytes, size_t cap, size_t *total, uint32_t *status);
+int crdt_map_nested_ops_egress(crdt_ctx *ctx, const crdt_map_nested_ops *ops, size_t N, const uint32_t *actors, size_t A,
+                               const uint32_t *keys, size_t K, const uint32_t *idict, size_t K2, uint64_t *frame_off,
+                               uint8_t *bytes, size_t cap, size_t *total, uint32_t *status);
+
 /* ---- synthetic inputs (bench / test data, generated in HBM) --------------------------------
  * Counter-based and reproducible on the CPU (oracle/oracle.py synth_* restates them; small
  * fixtures of both are pinned by tests/golden/make_golden.py -> tests/golden/synth.json).

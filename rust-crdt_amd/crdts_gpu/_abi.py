@@ -64,6 +64,8 @@ EXPORTS = (
     "crdt_orswot_read", "crdt_orswot_contains", "crdt_mvreg_read", "crdt_map_read", "crdt_map_get",
     "crdt_vclock_derive_add",
     "crdt_orswot_ops_ingest", "crdt_map_ops_ingest", "crdt_orswot_ops_egress", "crdt_map_ops_egress",
+    "crdt_map_counter_ops_ingest", "crdt_map_orswot_ops_ingest", "crdt_map_nested_ops_ingest",
+    "crdt_map_counter_ops_egress", "crdt_map_orswot_ops_egress", "crdt_map_nested_ops_egress",
 )
 
 
@@ -172,6 +174,24 @@ class MapOpsBuf(ctypes.Structure):  # crdt_map_ops_buf: MapOps with capacities f
     _fields_ = [("op_cap", S), ("op_off", P), ("kind", P), ("actor", P), ("counter", P), ("key", P), ("val", P),
                 ("clk_row", P), ("clk_pool", P), ("row_cap", S), ("key_off", P), ("keys", P),
                 ("id_cap", S)]
+
+
+class MapCounterOpsBuf(ctypes.Structure):  # crdt_map_counter_ops_buf: MapCounterOps with capacities for counts
+    _fields_ = [("op_cap", S), ("op_off", P), ("kind", P), ("actor", P), ("counter", P), ("key", P), ("vactor", P),
+                ("vcounter", P), ("vdir", P), ("clk_row", P), ("clk_pool", P), ("row_cap", S), ("key_off", P),
+                ("keys", P), ("key_cap", S)]
+
+
+class MapOrswotOpsBuf(ctypes.Structure):  # crdt_map_orswot_ops_buf: MapOrswotOps with capacities for counts
+    _fields_ = [("op_cap", S), ("op_off", P), ("kind", P), ("actor", P), ("counter", P), ("key", P), ("vkind", P),
+                ("vactor", P), ("vcounter", P), ("clk_row", P), ("clk_pool", P), ("row_cap", S), ("key_off", P),
+                ("keys", P), ("key_cap", S), ("mem_off", P), ("mems", P), ("mem_cap", S)]
+
+
+class MapNestedOpsBuf(ctypes.Structure):  # crdt_map_nested_ops_buf: MapNestedOps with capacities for counts
+    _fields_ = [("op_cap", S), ("op_off", P), ("kind", P), ("actor", P), ("counter", P), ("key", P), ("ikind", P),
+                ("iactor", P), ("icounter", P), ("ikey", P), ("val", P), ("ikeys", P), ("clk_row", P),
+                ("clk_pool", P), ("row_cap", S), ("key_off", P), ("keys", P), ("key_cap", S)]
 
 
 class MapDeferred(ctypes.Structure):  # crdt_map_deferred
@@ -400,6 +420,18 @@ _SIGS.update({  # op streams on the wire (csrc/wire_ops.hip)
     "crdt_orswot_ops_egress": ([P, ctypes.POINTER(OrswotOps), S, P, S, P, S, P, P, S, ctypes.POINTER(S), P],
                                ctypes.c_int),
     "crdt_map_ops_egress": ([P, ctypes.POINTER(MapOps), S, P, S, P, S, P, P, S, ctypes.POINTER(S), P], ctypes.c_int),
+    "crdt_map_counter_ops_ingest": ([P, P, P, S, P, S, P, S, ctypes.c_int, ctypes.POINTER(MapCounterOpsBuf), P, P, P,
+                                     ctypes.POINTER(U64)], ctypes.c_int),
+    "crdt_map_orswot_ops_ingest": ([P, P, P, S, P, S, P, S, P, S, ctypes.POINTER(MapOrswotOpsBuf), P, P, P, P,
+                                    ctypes.POINTER(U64)], ctypes.c_int),
+    "crdt_map_nested_ops_ingest": ([P, P, P, S, P, S, P, S, P, S, ctypes.POINTER(MapNestedOpsBuf), P, P, P,
+                                    ctypes.POINTER(U64)], ctypes.c_int),
+    "crdt_map_counter_ops_egress": ([P, ctypes.POINTER(MapCounterOps), S, P, S, P, S, ctypes.c_int, P, P, S,
+                                     ctypes.POINTER(S), P], ctypes.c_int),
+    "crdt_map_orswot_ops_egress": ([P, ctypes.POINTER(MapOrswotOps), S, P, S, P, S, P, S, P, P, S, ctypes.POINTER(S), P],
+                                   ctypes.c_int),
+    "crdt_map_nested_ops_egress": ([P, ctypes.POINTER(MapNestedOps), S, P, S, P, S, P, S, P, P, S, ctypes.POINTER(S), P],
+                                   ctypes.c_int),
 })
 for _t in ("vclock", "gcounter", "pncounter", "gset"):
     _SIGS[f"crdt_{_t}_lub_many_sharded"] = ([P, P, S, S, S, S, S, P], ctypes.c_int)

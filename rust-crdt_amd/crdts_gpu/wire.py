@@ -13,7 +13,10 @@ holding u64 ids).  Nothing here runs on the host except the shape checks.
 Op streams travel the same way (one Vec<Op> frame per state, Orswot<u64, u32> and
 Map<u32, MVReg<u64, u32>, u32>): orswot_ops_ingest / map_ops_ingest return the OrswotOpBatch /
 MapOpBatch that orswot.apply_batch / map.apply_batch take, orswot_ops_egress / map_ops_egress write
-such a batch as frames.
+such a batch as frames.  The value-typed Maps (Map<u32, GCounter / PNCounter / Orswot<u64, u32> /
+Map<u32, MVReg<u64, u32>, u32>, u32>) have map_counter_ops_ingest / map_orswot_ops_ingest /
+map_nested_ops_ingest and the three *_ops_egress twins, over the batches map.counter_apply_batch /
+orswot_apply_batch / nested_apply_batch take.
 """
 from __future__ import annotations
 
@@ -638,3 +641,232 @@ def map_ops_egress(ops, actors: torch.Tensor, keys: torch.Tensor, ctx: Optional[
     o.key, o.val, o.clk_row, o.clk_pool = dptr(ops.key), dptr(ops.val), dptr(ops.clk_row), dptr(ops.clk_pool)
     o.n_clk_rows, o.key_off, o.keys, o.n_keys = ops.clk_pool.shape[0], dptr(ops.key_off), dptr(ops.keys), ops.keys.shape[0]
     return _ops_egress(what, "crdt_map_ops_egress", o, ops, N, actors, keys, ctx)
+
+
+# ---- the value-typed Maps' op streams (include/crdt_gpu.h "value-typed Maps' op streams") -----------
+class VMapOpsIngest(NamedTuple):
+    """Result of map_counter_ops_ingest / map_orswot_ops_ingest / map_nested_ops_ingest."""
+    batch: tuple                        # map.MapCounterOpBatch / MapOrswotOpBatch / MapNestedOpBatch, as *_apply_batch takes it
+    status: torch.Tensor                # (N,) int32: BAD / MISSING / CAP bits
+    row_off: torch.Tensor               # (N+1,) int64: the state's first clock row
+    key_first: torch.Tensor             # (N+1,) int64: the state's first keyset key
+    mem_first: Optional[torch.Tensor]   # (N+1,) int64: the state's first member (Orswot Map only)
+    totals: Optional[tuple]             # (ops, rows, keys, mems) of the well-formed frames; None with sync=False
+
+
+_U8 = (torch.uint8,)
+_VOPS_DTYPES = {"kind": _U8, "vdir": _U8, "vkind": _U8, "ikind": _U8, "actor": _I32, "key": _I32, "vactor": _I32,
+                "iactor": _I32, "ikey": _I32, "clk_row": _I32, "keys": _I32, "mems": _I32}  # the rest: 64-bit
+
+
+def _vops_caps(what, sync, caps, n):
+    if sync:
+        if caps is not None:
+            raise ValueError(f"{what}: capacities are chosen by the sizing call unless sync=False")
+        return None
+    if caps is None or len(caps) != n or any(int(c) < 0 for c in caps):
+        names = "(op_cap, row_cap, key_cap, mem_cap)" if n == 4 else "(op_cap, row_cap, key_cap)"
+        raise ValueError(f"{what}: sync=False needs caps={names}")
+    return tuple(int(c) for c in caps)
+
+
+def _vops_frames(what, data, frame_off, actors, keys, third=None, third_dt=None, third_nm=None):
+    dicts = [(actors, "actors", (torch.int32,)), (keys, "keys", (torch.int32,))]
+    if third_nm:
+        dicts.append((third, third_nm, (third_dt,)))
+    _ops_check(what, [(data, "bytes", (torch.uint8,)), (frame_off, "frame_off", (torch.int64,))] + dicts)
+    if data.dim() != 1 or frame_off.dim() != 1 or frame_off.shape[0] < 1:
+        raise ValueError(f"{what}: bytes must be a uint8 vector and frame_off an int64 (N+1,) tensor")
+    if any(d.dim() != 1 or d.shape[0] == 0 for d, _, _ in dicts):
+        raise ValueError(f"{what}: the dictionaries must be non-empty vectors")
+    return frame_off.shape[0] - 1
+
+
+def _vops_ingest(what, fn, buf_cls, batch_cls, data, frame_off, N, A, dict_args, K2w, sync, caps, ctx):
+    """The sizing call (sync) or the caller's capacities, then the fill: the batch is allocated as the
+    host encoders of map.py leave it (one zero row / id where a pool would be empty)."""
+    ctx = _ctx(data, ctx)
+    dev = data.device
+    has_mem = "mems" in batch_cls._fields
+    e = lambda n, dt: torch.empty(n, dtype=dt, device=dev)  # noqa: E731
+    status = e(N, torch.int32)
+    op_off, row_off, key_first = (e(N + 1, torch.int64) for _ in range(3))
+    mem_first = e(N + 1, torch.int64) if has_mem else None
+    head = (_ptr_or_dummy(data), dptr(frame_off), N, *dict_args)
+    firsts = (dptr(row_off), dptr(key_first)) + ((dptr(mem_first),) if has_mem else ())
+    totals = None
+    if sync:
+        tot = (ctypes.c_uint64 * 4)()
+        if N:
+            ctx.call(fn, *head, None, *((None,) * len(firsts)), dptr(status), tot)
+        totals = tuple(int(x) for x in tot)
+        caps = totals
+    n_op, n_row, n_key = caps[:3]
+    n_mem = caps[3] if has_mem else 0
+    t = {}
+    for nm in batch_cls._fields:
+        if nm in ("op_off", "clk_pool", "key_off", "keys", "mem_off", "mems", "ikeys"):
+            continue
+        t[nm] = e(n_op, _VOPS_DTYPES.get(nm, _I64)[0])
+    t["op_off"] = op_off
+    t["clk_pool"] = torch.empty((max(n_row, 1), A), dtype=torch.int64, device=dev)
+    t["key_off"], t["keys"] = e(n_op + 1, torch.int64), e(max(n_key, 1), torch.int32)
+    if has_mem:
+        t["mem_off"], t["mems"] = e(n_op + 1, torch.int64), e(max(n_mem, 1), torch.int32)
+    if "ikeys" in batch_cls._fields:
+        t["ikeys"] = e(n_op, torch.int64) if K2w == 1 else torch.empty((n_op, K2w), dtype=torch.int64, device=dev)
+    if n_row == 0:
+        t["clk_pool"].zero_()
+    if n_key == 0:
+        t["keys"].zero_()
+    if has_mem and n_mem == 0:
+        t["mems"].zero_()
+    b = buf_cls()
+    b.op_cap, b.row_cap, b.key_cap = n_op, n_row, n_key
+    if has_mem:
+        b.mem_cap = n_mem
+    for nm in batch_cls._fields:
+        setattr(b, nm, dptr(t[nm]))
+    if N:
+        ctx.call(fn, *head, ctypes.byref(b), *firsts, dptr(status), None)
+    else:
+        for x in (op_off, row_off, key_first, t["key_off"][:1]) + ((mem_first, t["mem_off"][:1]) if has_mem else ()):
+            x.zero_()
+    return VMapOpsIngest(batch_cls(*(t[nm] for nm in batch_cls._fields)), status, row_off, key_first, mem_first, totals)
+
+
+def map_counter_ops_ingest(data: torch.Tensor, frame_off: torch.Tensor, actors: torch.Tensor, keys: torch.Tensor,
+                           pn: bool = False, sync: bool = True, caps=None, ctx: Optional[Context] = None) -> VMapOpsIngest:
+    """Frames of Vec<map::Op<u32, GCounter, u32>> (pn=False) or Vec<map::Op<u32, PNCounter, u32>> (pn=True),
+    one per state -> VMapOpsIngest with a map.MapCounterOpBatch for map.counter_apply_batch.  sync=True
+    sizes first (one host synchronisation) and allocates exactly; sync=False takes caps=(op_cap, row_cap,
+    key_cap), never synchronises, and marks states past a capacity with CAP."""
+    from .map import MapCounterOpBatch
+    what = "wire.map_counter_ops_ingest"
+    caps = _vops_caps(what, sync, caps, 3)
+    N = _vops_frames(what, data, frame_off, actors, keys)
+    A, K = actors.shape[0], keys.shape[0]
+    return _vops_ingest(what, "crdt_map_counter_ops_ingest", _abi.MapCounterOpsBuf, MapCounterOpBatch, data, frame_off,
+                        N, A, (dptr(actors), A, dptr(keys), K, 1 if pn else 0), 1, sync, caps, ctx)
+
+
+def map_orswot_ops_ingest(data: torch.Tensor, frame_off: torch.Tensor, actors: torch.Tensor, keys: torch.Tensor,
+                          members: torch.Tensor, sync: bool = True, caps=None,
+                          ctx: Optional[Context] = None) -> VMapOpsIngest:
+    """Frames of Vec<map::Op<u32, Orswot<u64, u32>, u32>> -> VMapOpsIngest with a map.MapOrswotOpBatch for
+    map.orswot_apply_batch (members: the sorted u64 member dictionary, int64; sync=False:
+    caps=(op_cap, row_cap, key_cap, mem_cap))."""
+    from .map import MapOrswotOpBatch
+    what = "wire.map_orswot_ops_ingest"
+    caps = _vops_caps(what, sync, caps, 4)
+    N = _vops_frames(what, data, frame_off, actors, keys, members, torch.int64, "members")
+    A, K, M = actors.shape[0], keys.shape[0], members.shape[0]
+    return _vops_ingest(what, "crdt_map_orswot_ops_ingest", _abi.MapOrswotOpsBuf, MapOrswotOpBatch, data, frame_off,
+                        N, A, (dptr(actors), A, dptr(keys), K, dptr(members), M), 1, sync, caps, ctx)
+
+
+def _k2w(K2: int) -> int:
+    return (K2 + 63) // 64 if K2 > 64 else 1
+
+
+def map_nested_ops_ingest(data: torch.Tensor, frame_off: torch.Tensor, actors: torch.Tensor, keys: torch.Tensor,
+                          idict: torch.Tensor, sync: bool = True, caps=None,
+                          ctx: Optional[Context] = None) -> VMapOpsIngest:
+    """Frames of Vec<map::Op<u32, Map<u32, MVReg<u64, u32>, u32>, u32>> -> VMapOpsIngest with a
+    map.MapNestedOpBatch for map.nested_apply_batch (idict: the sorted u32 inner-key dictionary, at most
+    256 entries; its size decides the ikeys mask's shape, (n_ops,) up to 64 and (n_ops, ceil(K2/64))
+    past it; sync=False: caps=(op_cap, row_cap, key_cap))."""
+    from .map import MapNestedOpBatch
+    what = "wire.map_nested_ops_ingest"
+    caps = _vops_caps(what, sync, caps, 3)
+    N = _vops_frames(what, data, frame_off, actors, keys, idict, torch.int32, "idict")
+    A, K, K2 = actors.shape[0], keys.shape[0], idict.shape[0]
+    return _vops_ingest(what, "crdt_map_nested_ops_ingest", _abi.MapNestedOpsBuf, MapNestedOpBatch, data, frame_off,
+                        N, A, (dptr(actors), A, dptr(keys), K, dptr(idict), K2), _k2w(K2), sync, caps, ctx)
+
+
+def _vops_batch(what, ops, batch_cls, o, actors, keys, third=None, third_dt=None, third_nm=None):
+    """Check an op batch before egress and fill the const struct `o` from it; returns (N, dictionary args)."""
+    if not hasattr(ops, "_fields") or tuple(ops._fields) != batch_cls._fields:
+        raise ValueError(f"{what}: expected an op batch with fields {batch_cls._fields}")
+    dicts = [(actors, "actors", (torch.int32,)), (keys, "keys_dict", (torch.int32,))]
+    if third_nm:
+        dicts.append((third, third_nm, (third_dt,)))
+    _ops_check(what, [(t, nm, _VOPS_DTYPES.get(nm, _I64)) for nm, t in zip(ops._fields, ops)] + dicts)
+    if any(d.dim() != 1 or d.shape[0] == 0 for d, _, _ in dicts):
+        raise ValueError(f"{what}: the dictionaries must be non-empty vectors")
+    n = ops.kind.shape[0]
+    if (ops.op_off.dim() != 1 or ops.op_off.shape[0] < 1 or ops.clk_pool.dim() != 2
+            or ops.clk_pool.shape[1] != actors.shape[0]):
+        raise ValueError(f"{what}: op_off (N+1,) and clk_pool (rows, A) expected")
+    K2w = _k2w(third.shape[0]) if third_nm == "idict" else 1
+    for nm, t in zip(ops._fields, ops):
+        if nm in ("mem_off", "key_off"):
+            if t.dim() != 1 or t.shape[0] < n + 1:
+                raise ValueError(f"{what}: {nm} needs n_ops+1 entries")
+        elif nm == "ikeys":
+            if tuple(t.shape) != ((n,) if K2w == 1 else (n, K2w)):
+                raise ValueError(f"{what}: ops.ikeys must be (n_ops,) or, past 64 inner keys, (n_ops, {K2w})")
+        elif nm in ("keys", "mems"):
+            if t.dim() != 1:
+                raise ValueError(f"{what}: ops.{nm} must be a vector")
+        elif nm not in ("op_off", "clk_pool") and tuple(t.shape) != (n,):
+            raise ValueError(f"{what}: ops.{nm} must have n_ops entries")
+    o.n_ops = n
+    for nm, t in zip(ops._fields, ops):
+        setattr(o, nm, dptr(t))
+    o.n_clk_rows, o.n_keys = ops.clk_pool.shape[0], ops.keys.shape[0]
+    if "mems" in ops._fields:
+        o.n_mems = ops.mems.shape[0]
+    return ops.op_off.shape[0] - 1
+
+
+def _vops_egress(fn, o, ops, N, dict_args, ctx):
+    ctx = _ctx(ops.op_off, ctx)
+    dev = ops.op_off.device
+    status = torch.empty(N, dtype=torch.int32, device=dev)
+    frame_off = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+    total = ctypes.c_size_t()
+    args = (ctypes.byref(o), N, *dict_args)
+    ctx.call(fn, *args, dptr(frame_off), None, 0, ctypes.byref(total), dptr(status))
+    data = torch.empty(max(total.value, 1), dtype=torch.uint8, device=dev)
+    ctx.call(fn, *args, dptr(frame_off), dptr(data), data.numel(), ctypes.byref(total), dptr(status))
+    return frame_off, data[:total.value], status
+
+
+def map_counter_ops_egress(ops, actors: torch.Tensor, keys: torch.Tensor, pn: bool = False,
+                           ctx: Optional[Context] = None):
+    """map.MapCounterOpBatch -> (frame_off (N+1,), bytes, status (N,) int32): one frame per state of
+    Vec<map::Op<u32, GCounter, u32>> (pn=False: an op with vdir = 1 has no wire form) or of the PNCounter
+    Map's ops (pn=True).  status bit 1 (MISSING): the state had an op with no wire form and its frame
+    is the empty Vec."""
+    from .map import MapCounterOpBatch
+    what = "wire.map_counter_ops_egress"
+    o = _abi.MapCounterOps()
+    N = _vops_batch(what, ops, MapCounterOpBatch, o, actors, keys)
+    return _vops_egress("crdt_map_counter_ops_egress", o, ops, N,
+                        (dptr(actors), actors.shape[0], dptr(keys), keys.shape[0], 1 if pn else 0), ctx)
+
+
+def map_orswot_ops_egress(ops, actors: torch.Tensor, keys: torch.Tensor, members: torch.Tensor,
+                          ctx: Optional[Context] = None):
+    """map.MapOrswotOpBatch -> (frame_off, bytes, status): frames of Vec<map::Op<u32, Orswot<u64, u32>, u32>>
+    (member lists and keysets in list order)."""
+    from .map import MapOrswotOpBatch
+    what = "wire.map_orswot_ops_egress"
+    o = _abi.MapOrswotOps()
+    N = _vops_batch(what, ops, MapOrswotOpBatch, o, actors, keys, members, torch.int64, "members")
+    return _vops_egress("crdt_map_orswot_ops_egress", o, ops, N,
+                        (dptr(actors), actors.shape[0], dptr(keys), keys.shape[0], dptr(members), members.shape[0]), ctx)
+
+
+def map_nested_ops_egress(ops, actors: torch.Tensor, keys: torch.Tensor, idict: torch.Tensor,
+                          ctx: Optional[Context] = None):
+    """map.MapNestedOpBatch -> (frame_off, bytes, status): frames of Vec<map::Op<u32, Map<u32, MVReg>, u32>>
+    (an inner Rm's mask bits ascending: the BTreeSet's order)."""
+    from .map import MapNestedOpBatch
+    what = "wire.map_nested_ops_egress"
+    o = _abi.MapNestedOps()
+    N = _vops_batch(what, ops, MapNestedOpBatch, o, actors, keys, idict, torch.int32, "idict")
+    return _vops_egress("crdt_map_nested_ops_egress", o, ops, N,
+                        (dptr(actors), actors.shape[0], dptr(keys), keys.shape[0], dptr(idict), idict.shape[0]), ctx)

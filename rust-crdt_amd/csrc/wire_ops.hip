@@ -21,7 +21,7 @@
 // into the op's SoA slots and its zeroed clock row).  The count pass settles malformed frames and,
 // through finalize, capacities, so the fill pass writes only whole, valid states.
 // Egress is count (lane = op) -> wave prefix sum -> scan over states -> write.
-#include "wire_common.hpp"
+#include "wire_ops_common.hpp"
 
 namespace crdt {
 
@@ -52,27 +52,6 @@ struct OpsPlan {
   uint32_t *ids;   // mem / keys
   uint32_t *key;   // Map
   u64 *val;        // Map
-};
-
-// MapWalk reads forward and expects the window it loads to be in flight already.  An op's id list
-// is skipped, not read, so the walk can land past everything issued: restart the ring there.
-struct OpWalk : MapWalk<> {
-  __device__ void seek(unsigned long long k, int lane) {
-    const unsigned long long wi = uni64(k) / kWalkWin;
-    if (wi != uni64(cur) && wi >= uni64(issued)) {
-      wire_vmcnt<0>();  // nothing of the windows skipped may land in a slot after it is reissued
-      issued = wi;
-      while (issued < nwin && issued < wi + kWalkRing) {
-        dma(issued, lane);
-        issued = uni64(issued + 1);
-      }
-    }
-  }
-  __device__ uint32_t at(unsigned long long k, int lane) {
-    seek(k, lane);
-    return get(k, lane);
-  }
-  __device__ u64 at64(unsigned long long k, int lane) { return (u64)at(k, lane) | ((u64)at(k + 1, lane) << 32); }
 };
 
 // The walk over one frame (nw >= 2 words): emit(pos, tag, n, cnt) for every op, in order, with pos

@@ -1,0 +1,29 @@
+// Shared by the op-stream wire kernels (wire_ops.hip: Orswot and Map<K, MVReg> ops; wire_vmap_ops.hip:
+// the value-typed Maps' ops): the frame walk's reader.
+#pragma once
+#include "wire_common.hpp"
+
+namespace crdt {
+
+// MapWalk reads forward and expects the window it loads to be in flight already.  An op's id list
+// is skipped, not read, so the walk can land past everything issued: restart the ring there.
+struct OpWalk : MapWalk<> {
+  __device__ void seek(unsigned long long k, int lane) {
+    const unsigned long long wi = uni64(k) / kWalkWin;
+    if (wi != uni64(cur) && wi >= uni64(issued)) {
+      wire_vmcnt<0>();  // nothing of the windows skipped may land in a slot after it is reissued
+      issued = wi;
+      while (issued < nwin && issued < wi + kWalkRing) {
+        dma(issued, lane);
+        issued = uni64(issued + 1);
+      }
+    }
+  }
+  __device__ uint32_t at(unsigned long long k, int lane) {
+    seek(k, lane);
+    return get(k, lane);
+  }
+  __device__ u64 at64(unsigned long long k, int lane) { return (u64)at(k, lane) | ((u64)at(k + 1, lane) << 32); }
+};
+
+}  // namespace crdt
