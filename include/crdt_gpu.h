@@ -1053,6 +1053,20 @@ int crdt_mvreg_merge_batch(crdt_ctx *ctx, const crdt_mvreg_states *self, const c
 int crdt_mvreg_apply_batch(crdt_ctx *ctx, const crdt_mvreg_states *states, const crdt_mvreg_ops *ops,
                            uint32_t *status);
 
+/* Batched Causal::forget of MVReg (mvreg.rs:88-104 with VClock::forget): register i forgets the
+ * clock y + i*y_stride (A counters; y_stride = 0: one clock for all registers, as in
+ * crdt_map_forget_batch), in place.  Every value clock keeps v[a] where v[a] > y[a] (an unsigned
+ * compare over the full u64 range) and becomes 0 elsewhere; a value whose clock empties is dropped.
+ * Result layout as above: the survivors in Vec order from slot 0, every slot past them an all-zero
+ * clock and value 0; empty slots of the input are skipped wherever they sit.  All of a register's
+ * slots are loaded before any is stored, so the compaction in place is safe.  A register the forget
+ * leaves bit-identical is not written.  status[i] (device u32, may be NULL) is written for every i;
+ * no bit is defined yet: 0.  Limits as merge_batch / apply_batch: A <= 1024, 1 <= V <= 16; A > 256
+ * or V > 8 run one workgroup per register, below that a register takes a sub-wave lane segment
+ * (one lane per 16 bytes of a row). */
+int crdt_mvreg_forget_batch(crdt_ctx *ctx, const crdt_mvreg_states *states, const uint64_t *y, size_t y_stride,
+                            uint32_t *status);
+
 /* ---- causal helpers on dense clock rows -----------------------------------
  * Row-pair ops over N pairs (x_i, y_i) of A-word rows (VClock, GCounter inner, or a PNCounter
  * P‖N row with A = 2·actors):
@@ -1498,6 +1512,70 @@ int crdt_map_orswot_ops_egress(crdt_ctx *ctx, const crdt_map_orswot_ops *ops, si
 int crdt_map_nested_ops_egress(crdt_ctx *ctx, const crdt_map_nested_ops *ops, size_t N, const uint32_t *actors, size_t A,
                                const uint32_t *keys, size_t K, const uint32_t *idict, size_t K2, uint64_t *frame_off,
                                uint8_t *bytes, size_t cap, size_t *total, uint32_t *status);
+
+/* ---- serde wire format of MVReg<u64, u32> on its own: states ----------------------------------------
+ * MVReg derives Serialize / Deserialize (mvreg.rs:32); these entry points read / write a register
+ * outside a Map:
+ *   MVReg<u64, u32> = u64 n, n x (VClock<u32> clock, u64 val), values in Vec order
+ * e.g. MVReg { vals: [({7: 3}, 10)] } is the 36 bytes (as 32-bit words) 1 0 | 1 0 | 7 3 0 | 10 0.
+ * Frames, the actor dictionary and alignment follow the state wire form above; device pointers only.
+ * Ingest fills `out` (N registers of A actors and V slots; strides honoured) and writes every slot
+ * of every register: the values kept from slot 0 in Vec order, the rest zero (nothing needs
+ * pre-zeroing).  status[s] (device u32, written for every s): bit 0 = malformed frame (truncated,
+ * trailing bytes, misaligned offset, a count that cannot fit the bytes left): the register is written
+ * empty; bit 1 = an actor missing from the dictionary: that record is skipped; bit 2 = more than V
+ * values: the first V are kept; bit 3 = a value whose clock is empty on the wire, or empties once
+ * unknown actors are skipped: it has no dense form (an all-zero row is an empty slot) and is dropped.
+ * Egress uses the sizing protocol of crdt_orswot_egress (*total always written; the bytes when `bytes`
+ * is non-NULL and cap >= *total; frame_off device, N+1) and writes occupied slots in slot order, clock
+ * records in ascending dictionary order.  Ingest -> egress reproduces byte for byte any well-formed
+ * frame whose actors are all in the dictionary and which has no empty-clock value and at most V
+ * values.  One wave per frame, through the register parser / writer of the Map frames.  Limit: A <= 4096. */
+int crdt_mvreg_ingest(crdt_ctx *ctx, const uint8_t *bytes, const uint64_t *frame_off, size_t N,
+                      const uint32_t *actors, size_t A, const crdt_mvreg_states *out, uint32_t *status);
+int crdt_mvreg_egress(crdt_ctx *ctx, const crdt_mvreg_states *states, const uint32_t *actors,
+                      uint64_t *frame_off, uint8_t *bytes, size_t cap, size_t *total);
+
+/* ---- serde wire format of MVReg<u64, u32> on its own: Put streams ------------------------------------
+ * mvreg::Op::Put derives serde (mvreg.rs:38-47):
+ *   mvreg::Op<u64, u32> = u32 0 (Put), VClock clock, u64 val
+ *   frame of register i = Vec<Op>: u64 n_ops, then the ops back to back
+ * e.g. Vec[Put { clock: {7: 3}, val: 10 }] is the 40 bytes (as words) 1 0 | 0 | 1 0 | 7 3 0 | 10 0.
+ * The contract is the one stated for crdt_orswot_ops_ingest, restricted to ops and rows.  Ingest fills
+ * a crdt_mvreg_ops_buf, the mutable twin of crdt_mvreg_ops with the same field order and sizes and
+ * capacities where the const struct holds counts: a filled buffer casts to crdt_mvreg_ops and goes to
+ * crdt_mvreg_apply_batch as is.  One clock row per op: clk_row[o] = o, rows == ops; clk_row / val
+ * hold op_cap entries, clk_pool row_cap x A (row_cap <= 2^32 - 1), op_off N+1.  Every element of the
+ * first n_ops entries is written by the call.  A Put with an empty clock is a valid op, kept with an
+ * all-zero row (MVReg::apply ignores it, mvreg.rs:136-138, and so does crdt_mvreg_apply_batch).
+ * totals (host, may be NULL): non-NULL = the call synchronises once and returns {ops, rows} of all
+ * well-formed frames; with out = NULL it only sizes.  NULL = no host synchronisation: capacities
+ * are enforced on the device with the prefix cut rule: the first register whose ops end past
+ * min(op_cap, row_cap) and every one after it get bit 2 and contribute no ops, so the registers kept
+ * are a prefix laid out exactly as an uncut call lays them out.  To size without a sync:
+ * ops <= (B_s - 8) / 20 (the smallest op, a Put with an empty clock, is 4 + 8 + 8 bytes).
+ * status[s] (device u32, written for every s): bit 0 = malformed frame (an unknown tag included): it
+ * contributes nothing and shifts no neighbour; bit 1 = a clock record's actor is missing: the record
+ * is skipped; bit 2 = capacity.
+ * Egress is count -> scan -> write with the sizing protocol above.  status[s] bit 1 = the register has
+ * an op with no wire form (clk_row >= n_clk_rows, or an invalid op_off): its frame is the empty Vec.
+ * Ingest -> egress is byte-identical for well-formed frames whose actors are all in the dictionary.
+ * No limit on A (a dictionary that does not fit beside the frame ring in 64 KiB of LDS is searched
+ * in global memory). */
+typedef struct crdt_mvreg_ops_buf { /* mutable twin of crdt_mvreg_ops: same field order and sizes */
+  size_t op_cap;
+  uint64_t *op_off;   /* [N+1]        */
+  uint32_t *clk_row;  /* [op_cap]     */
+  uint64_t *clk_pool; /* [row_cap][A] */
+  size_t row_cap;
+  uint64_t *val;      /* [op_cap]     */
+} crdt_mvreg_ops_buf;
+
+int crdt_mvreg_ops_ingest(crdt_ctx *ctx, const uint8_t *bytes, const uint64_t *frame_off, size_t N,
+                          const uint32_t *actors, size_t A, const crdt_mvreg_ops_buf *out, uint32_t *status,
+                          uint64_t *totals);
+int crdt_mvreg_ops_egress(crdt_ctx *ctx, const crdt_mvreg_ops *ops, size_t N, const uint32_t *actors, size_t A,
+                          uint64_t *frame_off, uint8_t *bytes, size_t cap, size_t *total, uint32_t *status);
 
 /* ---- synthetic inputs (bench / test data, generated in HBM) --------------------------------
  * Counter-based and reproducible on the CPU (oracle/oracle.py synth_* restates them; small

@@ -66,6 +66,8 @@ EXPORTS = (
     "crdt_orswot_ops_ingest", "crdt_map_ops_ingest", "crdt_orswot_ops_egress", "crdt_map_ops_egress",
     "crdt_map_counter_ops_ingest", "crdt_map_orswot_ops_ingest", "crdt_map_nested_ops_ingest",
     "crdt_map_counter_ops_egress", "crdt_map_orswot_ops_egress", "crdt_map_nested_ops_egress",
+    "crdt_mvreg_forget_batch", "crdt_mvreg_ingest", "crdt_mvreg_egress", "crdt_mvreg_ops_ingest",
+    "crdt_mvreg_ops_egress",
 )
 
 
@@ -218,6 +220,10 @@ class MVRegOut(ctypes.Structure):  # crdt_mvreg_out
 
 class MVRegOps(ctypes.Structure):  # crdt_mvreg_ops
     _fields_ = [("n_ops", S), ("op_off", P), ("clk_row", P), ("clk_pool", P), ("n_clk_rows", S), ("val", P)]
+
+
+class MVRegOpsBuf(ctypes.Structure):  # crdt_mvreg_ops_buf: MVRegOps with capacities for counts
+    _fields_ = [("op_cap", S), ("op_off", P), ("clk_row", P), ("clk_pool", P), ("row_cap", S), ("val", P)]
 
 
 # crdt_comm_ops: the caller's own collectives (host buffers)
@@ -435,6 +441,13 @@ _SIGS.update({  # op streams on the wire (csrc/wire_ops.hip)
 })
 for _t in ("vclock", "gcounter", "pncounter", "gset"):
     _SIGS[f"crdt_{_t}_lub_many_sharded"] = ([P, P, S, S, S, S, S, P], ctypes.c_int)
+_SIGS.update({  # MVReg on its own: forget and the wire forms (csrc/mvreg_forget.hip, csrc/wire_mvreg.hip)
+    "crdt_mvreg_forget_batch": ([P, ctypes.POINTER(MVRegStates), P, S, P], ctypes.c_int),
+    "crdt_mvreg_ingest": ([P, P, P, S, P, S, ctypes.POINTER(MVRegStates), P], ctypes.c_int),
+    "crdt_mvreg_egress": ([P, ctypes.POINTER(MVRegStates), P, P, P, S, ctypes.POINTER(S)], ctypes.c_int),
+    "crdt_mvreg_ops_ingest": ([P, P, P, S, P, S, ctypes.POINTER(MVRegOpsBuf), P, ctypes.POINTER(U64)], ctypes.c_int),
+    "crdt_mvreg_ops_egress": ([P, ctypes.POINTER(MVRegOps), S, P, S, P, P, S, ctypes.POINTER(S), P], ctypes.c_int),
+})
 for _t in ("vclock", "gcounter", "pncounter", "gset"):
     _SIGS[f"crdt_{_t}_lub_many"] = ([P, P, S, S, S, S, S, P, S, ctypes.c_uint], ctypes.c_int)
     _SIGS[f"crdt_{_t}_merge_batch"] = ([P, P, P, S, S, S, S], ctypes.c_int)

@@ -8,6 +8,9 @@ Dense register (the value layout of the Map entry points): slots in Vec order,
     merge_batch(self (N, V, A), other)               self[i].merge(other[i]), in place
     apply_batch(vclk (N, V, A), vval, ops)           reg[i].apply(op) for its ops in order   (mvreg.rs:130-166)
     read(vclk (N, V, A), vval)                       reg[i].read() as a ReadCtx              (mvreg.rs:183-215)
+    forget_batch(vclk (N, V, A), vval, y)            reg[i].forget(y or y[i]), in place      (mvreg.rs:88-104)
+The wire forms (register frames, Vec<Op::Put> frames) are in wire.py: mvreg_ingest / mvreg_egress /
+mvreg_ops_ingest / mvreg_ops_egress.
 """
 from __future__ import annotations
 
@@ -140,6 +143,25 @@ def apply_batch(vclk: torch.Tensor, vval: torch.Tensor, ops: MVRegOpBatch, ctx: 
                       ops.clk_pool.shape[0], ops.val.data_ptr())
     status = torch.empty(st.N, dtype=torch.int32, device=vclk.device)
     ctx.call("crdt_mvreg_apply_batch", ctypes.byref(st), ctypes.byref(o), status.data_ptr())
+    return status
+
+
+def forget_batch(vclk: torch.Tensor, vval: torch.Tensor, y: torch.Tensor, ctx: Optional[Context] = None) -> torch.Tensor:
+    """Causal::forget (mvreg.rs:88-104) in place on (N, V, A) / (N, V): register i forgets y (A,)
+    (one clock for all registers) or y[i] of (N, A).  Values whose clock empties are dropped, the
+    survivors move to the first slots in order.  Returns status (N,) int32 (no bit defined: 0)."""
+    _rc.check_args("mvreg.forget_batch", [(vclk, "vclk"), (vval, "vval"), (y, "y")])
+    ctx = ctx or Context.default(vclk.device.index)
+    st = _states(ctx, vclk, vval, "mvreg.forget_batch")
+    ctx.check_tensor(y, "mvreg.forget_batch(y)")
+    if y.dim() == 1 and y.shape[0] == st.A and y.stride(0) == 1:
+        ys = 0
+    elif y.dim() == 2 and tuple(y.shape) == (st.N, st.A) and y.stride(1) == 1 and (st.N <= 1 or y.stride(0) >= st.A):
+        ys = y.stride(0)
+    else:
+        raise ValueError(f"mvreg.forget_batch: y must be ({st.A},) or ({st.N}, {st.A}) with contiguous rows")
+    status = torch.empty(st.N, dtype=torch.int32, device=vclk.device)
+    ctx.call("crdt_mvreg_forget_batch", ctypes.byref(st), y.data_ptr(), ys, status.data_ptr())
     return status
 
 

@@ -17,6 +17,10 @@ such a batch as frames.  The value-typed Maps (Map<u32, GCounter / PNCounter / O
 Map<u32, MVReg<u64, u32>, u32>, u32>) have map_counter_ops_ingest / map_orswot_ops_ingest /
 map_nested_ops_ingest and the three *_ops_egress twins, over the batches map.counter_apply_batch /
 orswot_apply_batch / nested_apply_batch take.
+
+MVReg<u64, u32> on its own: mvreg_ingest / mvreg_egress move register frames to and from the dense
+(vclk, vval) of mvreg.py, mvreg_ops_ingest / mvreg_ops_egress Vec<mvreg::Op> frames to and from the
+MVRegOpBatch mvreg.apply_batch takes.
 """
 from __future__ import annotations
 
@@ -870,3 +874,143 @@ def map_nested_ops_egress(ops, actors: torch.Tensor, keys: torch.Tensor, idict: 
     N = _vops_batch(what, ops, MapNestedOpBatch, o, actors, keys, idict, torch.int32, "idict")
     return _vops_egress("crdt_map_nested_ops_egress", o, ops, N,
                         (dptr(actors), actors.shape[0], dptr(keys), keys.shape[0], dptr(idict), idict.shape[0]), ctx)
+
+
+# ---- MVReg<u64, u32> on its own (include/crdt_gpu.h "MVReg<u64, u32> on its own") -------------------
+EMPTY_CLOCK = 8  # mvreg_ingest status bit 3: a value with an empty clock was dropped
+
+
+class MVRegOpsIngest(NamedTuple):
+    """Result of mvreg_ops_ingest."""
+    ops: tuple                # mvreg.MVRegOpBatch: goes to mvreg.apply_batch unchanged
+    status: torch.Tensor      # (N,) int32: BAD / MISSING / CAP bits
+    totals: Optional[tuple]   # (ops, rows) of the well-formed frames; None with sync=False
+
+
+def _mvreg_frames(what, data, frame_off, actors):
+    _ops_check(what, ((data, "bytes", (torch.uint8,)), (frame_off, "frame_off", (torch.int64,)),
+                      (actors, "actors", (torch.int32,))))
+    if data.dim() != 1 or frame_off.dim() != 1 or frame_off.shape[0] < 1:
+        raise ValueError(f"{what}: bytes must be a uint8 vector and frame_off an int64 (N+1,) tensor")
+    if actors.dim() != 1 or actors.shape[0] == 0:
+        raise ValueError(f"{what}: the actor dictionary must be a non-empty vector")
+    return frame_off.shape[0] - 1, actors.shape[0]
+
+
+def _mvreg_states(what, vclk, vval, actors):
+    for t, nm in ((vclk, "vclk"), (vval, "vval")):  # (registers may be strided: no contiguity asked here)
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{what}({nm}): expected a torch.Tensor")
+        if t.dtype not in _I64:
+            raise ValueError(f"{what}({nm}): dtype {t.dtype}; expected one of {_I64}")
+    _ops_check(what, ((actors, "actors", (torch.int32,)),))
+    for t, nm in ((vclk, "vclk"), (vval, "vval")):
+        if t.device != actors.device:
+            raise ValueError(f"{what}({nm}): tensor on {t.device}; expected a cuda tensor on {actors.device}")
+    if vclk.dim() != 3 or vval.dim() != 2 or tuple(vclk.shape[:2]) != tuple(vval.shape):
+        raise ValueError(f"{what}: vclk (N, V, A) and vval (N, V) expected")
+    N, V, A = vclk.shape
+    if actors.dim() != 1 or actors.shape[0] != A or A == 0 or V == 0:
+        raise ValueError(f"{what}: the actor dictionary must hold A = {A} >= 1 ids and V >= 1")
+    if vclk.stride(2) != 1 or vclk.stride(1) != A or vval.stride(1) != 1:
+        raise ValueError(f"{what}: each register's slots must be packed")
+    return _abi.MVRegStates(N, A, V, vclk.data_ptr(), vclk.stride(0), vval.data_ptr(), vval.stride(0))
+
+
+def mvreg_ingest(data: torch.Tensor, frame_off: torch.Tensor, actors: torch.Tensor, V: int,
+                 ctx: Optional[Context] = None):
+    """MVReg<u64, u32> frames -> (vclk (N, V, A) int64, vval (N, V) int64, status (N,) int32): the
+    values in Vec order from slot 0, the rest zero.  status bits BAD / MISSING / CAP (more than V
+    values: the first V kept) / EMPTY_CLOCK (a value with an empty clock: dropped)."""
+    what = "wire.mvreg_ingest"
+    N, A = _mvreg_frames(what, data, frame_off, actors)
+    if int(V) < 1:
+        raise ValueError(f"{what}: V >= 1 value slots")
+    ctx = _ctx(data, ctx)
+    dev = data.device
+    vclk = torch.empty((N, int(V), A), dtype=torch.int64, device=dev)
+    vval = torch.empty((N, int(V)), dtype=torch.int64, device=dev)
+    status = torch.empty(N, dtype=torch.int32, device=dev)
+    st = _abi.MVRegStates(N, A, int(V), vclk.data_ptr(), int(V) * A, vval.data_ptr(), int(V))
+    ctx.call("crdt_mvreg_ingest", _ptr_or_dummy(data), dptr(frame_off), N, dptr(actors), A, ctypes.byref(st),
+             dptr(status))
+    return vclk, vval, status
+
+
+def mvreg_egress(vclk: torch.Tensor, vval: torch.Tensor, actors: torch.Tensor, ctx: Optional[Context] = None):
+    """Dense registers (vclk (N, V, A), vval (N, V)) -> (frame_off (N+1,), bytes) of MVReg frames:
+    occupied slots in slot order."""
+    st = _mvreg_states("wire.mvreg_egress", vclk, vval, actors)
+    ctx = _ctx(vclk, ctx)
+    return _egress(ctx, "crdt_mvreg_egress", st.N, vclk.device, ctypes.byref(st), dptr(actors))
+
+
+def mvreg_ops_ingest(data: torch.Tensor, frame_off: torch.Tensor, actors: torch.Tensor, sync: bool = True, caps=None,
+                     ctx: Optional[Context] = None) -> MVRegOpsIngest:
+    """Frames of Vec<mvreg::Op<u64, u32>> (one per register) -> MVRegOpsIngest with a
+    mvreg.MVRegOpBatch.  sync=True sizes first (one host synchronisation) and allocates exactly;
+    sync=False takes caps=(op_cap, row_cap), never synchronises, and marks the registers past a
+    capacity with CAP."""
+    from .mvreg import MVRegOpBatch
+    what = "wire.mvreg_ops_ingest"
+    if sync:
+        if caps is not None:
+            raise ValueError(f"{what}: capacities are chosen by the sizing call unless sync=False")
+    elif caps is None or len(caps) != 2 or any(int(c) < 0 for c in caps):
+        raise ValueError(f"{what}: sync=False needs caps=(op_cap, row_cap)")
+    N, A = _mvreg_frames(what, data, frame_off, actors)
+    ctx = _ctx(data, ctx)
+    dev = data.device
+    status = torch.empty(N, dtype=torch.int32, device=dev)
+    op_off = torch.empty(N + 1, dtype=torch.int64, device=dev)
+    head = (_ptr_or_dummy(data), dptr(frame_off), N, dptr(actors), A)
+    totals = None
+    if sync:  # size, then fill with exactly enough room (+ one pad row, as encode_ops leaves)
+        tot = (ctypes.c_uint64 * 2)()
+        if N:
+            ctx.call("crdt_mvreg_ops_ingest", *head, None, dptr(status), tot)
+        totals = (int(tot[0]), int(tot[1]))
+        caps = totals
+    n_op, n_row = int(caps[0]), int(caps[1])
+    row = torch.empty(n_op, dtype=torch.int32, device=dev)
+    val = torch.empty(n_op, dtype=torch.int64, device=dev)
+    pool = torch.empty((n_row + 1, A), dtype=torch.int64, device=dev)
+    pool[n_row].zero_()
+    b = _abi.MVRegOpsBuf(n_op, dptr(op_off), dptr(row), dptr(pool), n_row, dptr(val))
+    if N:
+        ctx.call("crdt_mvreg_ops_ingest", *head, ctypes.byref(b), dptr(status), None)
+    else:
+        op_off.zero_()
+    return MVRegOpsIngest(MVRegOpBatch(op_off, row, pool, val), status, totals)
+
+
+def mvreg_ops_egress(ops, actors: torch.Tensor, ctx: Optional[Context] = None):
+    """mvreg.MVRegOpBatch -> (frame_off (N+1,), bytes, status (N,) int32): one Vec<mvreg::Op> frame
+    per register.  status bit 1 (MISSING): the register had an op with no wire form (clk_row out of
+    range, an invalid op_off) and its frame is the empty Vec."""
+    from .mvreg import MVRegOpBatch
+    what = "wire.mvreg_ops_egress"
+    if not hasattr(ops, "_fields") or tuple(ops._fields) != MVRegOpBatch._fields:
+        raise ValueError(f"{what}: expected an op batch with fields {MVRegOpBatch._fields}")
+    _ops_check(what, ((ops.op_off, "op_off", _I64), (ops.clk_row, "clk_row", _I32), (ops.clk_pool, "clk_pool", _I64),
+                      (ops.val, "val", _I64), (actors, "actors", (torch.int32,))))
+    n = ops.val.shape[0]
+    if actors.dim() != 1 or actors.shape[0] == 0:
+        raise ValueError(f"{what}: the actor dictionary must be a non-empty vector")
+    if ops.op_off.dim() != 1 or ops.op_off.shape[0] < 1 or ops.clk_pool.dim() != 2 \
+            or ops.clk_pool.shape[1] != actors.shape[0] or tuple(ops.clk_row.shape) != (n,) or ops.val.dim() != 1:
+        raise ValueError(f"{what}: op_off (N+1,), clk_row / val (n_ops,) and clk_pool (rows, A) expected")
+    N = ops.op_off.shape[0] - 1
+    o = _abi.MVRegOps(n, dptr(ops.op_off), _ptr_or_dummy(ops.clk_row), _ptr_or_dummy(ops.clk_pool),
+                      ops.clk_pool.shape[0], _ptr_or_dummy(ops.val))
+    ctx = _ctx(ops.op_off, ctx)
+    dev = ops.op_off.device
+    status = torch.empty(N, dtype=torch.int32, device=dev)
+    args = (ctypes.byref(o), N, dptr(actors), actors.shape[0])
+    frame_off = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+    total = ctypes.c_size_t()
+    ctx.call("crdt_mvreg_ops_egress", *args, dptr(frame_off), None, 0, ctypes.byref(total), dptr(status))
+    data = torch.empty(max(total.value, 1), dtype=torch.uint8, device=dev)
+    ctx.call("crdt_mvreg_ops_egress", *args, dptr(frame_off), dptr(data), data.numel(), ctypes.byref(total),
+             dptr(status))
+    return frame_off, data[:total.value], status

@@ -83,6 +83,7 @@ struct Tune {
   int pair_occ = 1;            // ... cap on workgroups per CU (LDS padding; 0 = none): one workgroup
                                //     per CU keeps fewer HBM requests in flight, 69% -> 74-75% of 8 TB/s
   int map_forget_bpc = 1;      // Map forget, 16-byte kernel: workgroups per CU (1: 67% of 8 TB/s vs 64% at 4)
+  int mvreg_forget_bpc = 32;   // MVReg forget, sub-wave segment kernel: workgroups per CU of its grid-stride loop
   int map_pair_pf = 0;         // Map merge_batch sub-wave key pass: the next keys' rows loaded before the merge
                                //     (opt-in: 5.86 vs 5.81 ms at 4 waves/SIMD, profiles/r04_map_pair_pf_ab.log)
   int map_pair_nt = 1;         // ... sub-wave key pass: key rows loaded / stored non-temporal (5.14 -> 5.00 ms,

@@ -265,6 +265,7 @@ static void apply_tune(crdt_ctx *ctx, const char *t) {
       else if (k == "mflat" && v >= 0 && v <= 16) ctx->tune.merge_flat = v;
       else if (k == "mpbpc" && v >= 1 && v <= 4096) ctx->tune.map_pair_bpc = v;
       else if (k == "mfbpc" && v >= 1 && v <= 64) ctx->tune.map_forget_bpc = v;
+      else if (k == "mvfbpc" && v >= 1 && v <= 64) ctx->tune.mvreg_forget_bpc = v;
     }
     pos = end + 1;
   }

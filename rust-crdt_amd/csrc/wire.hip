@@ -639,28 +639,17 @@ __global__ __launch_bounds__(kBlock) void map_ingest_kernel(MapWirePlan p) {
         }
         if (ki >= 0) store_row<u64>(p.ec + (s * p.K + (unsigned long long)ki) * p.A, row, p.A, lane);
         wfence();
-        const u64 m = rd64(f.w, k);
-        k += 2;
-        for (u64 v = 0; v < m && k != ~0ull; ++v) {
-          k = parse_vclock(f, k, actors, p.A, row, lane, st);
-          if (k == ~0ull || k + 2 > f.nw) {
-            st |= kWireBad;
-            k = ~0ull;
-            break;
+        // the key's register: value v into slot v (wire_common.hpp)
+        k = parse_mvreg(f, k, actors, p.A, row, lane, st, [&](u64 v, u64 val) {
+          if (ki < 0) return;
+          if (v < p.V) {
+            const unsigned long long slot = (s * p.K + (unsigned long long)ki) * p.V + v;
+            store_row<u64>(p.vclk + slot * p.A, row, p.A, lane);
+            if (lane == 0) p.vval[slot] = val;
+          } else {
+            st |= kWireCap;
           }
-          const u64 val = rd64(f.w, k);
-          k += 2;
-          if (ki >= 0) {
-            if (v < p.V) {
-              const unsigned long long slot = (s * p.K + (unsigned long long)ki) * p.V + v;
-              store_row<u64>(p.vclk + slot * p.A, row, p.A, lane);
-              if (lane == 0) p.vval[slot] = val;
-            } else {
-              st |= kWireCap;
-            }
-          }
-          wfence();
-        }
+        });
       }
       if (k != ~0ull && k + 2 <= f.nw) {
         const u64 d = rd64(f.w, k);
@@ -1358,27 +1347,13 @@ __global__ __launch_bounds__(kBlock) void map_egress_kernel(MapWirePlan p, int w
       const u64 n = nnz_row(er, p.A, lane);
       if (n == 0) continue;
       const unsigned long long slot0 = (s * p.K + key) * p.V;
-      u64 m = 0, vsz = 0;
-      for (unsigned long long v = 0; v < p.V; ++v) {
-        const u64 nv = nnz_row(p.vclk + (slot0 + v) * p.A, p.A, lane);
-        if (nv) {
-          ++m;
-          vsz += 8 + 12 * nv + 8;
-        }
-      }
+      u64 m = 0;
+      const u64 vsz = mvreg_wire_size(p.vclk + slot0 * p.A, p.V, p.A, lane, m);
       sz += 4 + 8 + 12 * n + 8 + vsz;
       if (!write) continue;
       if (lane == 0) w[k] = p.keys[key];
       k = write_vclock(w, k + 1, er, p.A, p.actors, lane);
-      if (lane == 0) wr64(w, k, m);
-      k += 2;
-      for (unsigned long long v = 0; v < p.V; ++v) {
-        const u64 *vr = p.vclk + (slot0 + v) * p.A;
-        if (nnz_row(vr, p.A, lane) == 0) continue;
-        k = write_vclock(w, k, vr, p.A, p.actors, lane);
-        if (lane == 0) wr64(w, k, p.vval[slot0 + v]);
-        k += 2;
-      }
+      k = write_mvreg(w, k, p.vclk + slot0 * p.A, p.vval + slot0, p.V, p.A, p.actors, m, lane);
     }
     }
     const unsigned long long nd = p.def_count ? p.def_count[s] : 0;

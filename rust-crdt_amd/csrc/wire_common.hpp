@@ -1,5 +1,5 @@
 // Shared pieces of the serde wire kernels (wire.hip: the reference types and Map<K, MVReg>;
-// wire_vmap.hip: the value-typed Maps; wire_ops.hip: op streams): frame access, dictionary lookups, VClock parse / write.
+// wire_vmap.hip: the value-typed Maps; wire_ops.hip: op streams; wire_mvreg.hip: MVReg on its own): frame access, dictionary lookups, VClock parse / write.
 // The encoding (bincode 1.x, default options) is restated at the top of wire.hip.
 #pragma once
 #include "common.hpp"
@@ -117,6 +117,67 @@ __device__ inline unsigned long long write_vclock(uint32_t *w, unsigned long lon
     base += __popcll(m);
   }
   return k + 2 + 3 * n;
+}
+
+// ---- MVReg<u64, u32> = u64 m, m x (VClock, u64 val) (mvreg.rs:32-35) -------------------------------
+// The register of a Map entry (wire.hip) and a whole MVReg frame (wire_mvreg.hip) share these.
+//
+// Parse the register at word k: every value's clock goes through the LDS row, then put(v, val)
+// runs (wave-uniform, the row landed) and decides what becomes of value v.  Returns the word after
+// the register, or ~0 with st |= kWireBad on a truncated one.
+template <class F>
+__device__ __forceinline__ unsigned long long parse_mvreg(const Frame &f, unsigned long long k, const uint32_t *actors,
+                                                          unsigned long long A, u64 *row, int lane, unsigned &st,
+                                                          F &&put) {
+  if (k + 2 > f.nw) {
+    st |= kWireBad;
+    return ~0ull;
+  }
+  const u64 m = rd64(f.w, k);
+  k += 2;
+  for (u64 v = 0; v < m; ++v) {
+    k = parse_vclock(f, k, actors, A, row, lane, st);
+    if (k == ~0ull || k + 2 > f.nw) {
+      st |= kWireBad;
+      return ~0ull;
+    }
+    const u64 val = rd64(f.w, k);
+    k += 2;
+    put(v, val);
+    wfence();
+  }
+  return k;
+}
+
+// Bytes of the occupied slots' records (VClock, u64 val) of the V dense slots at vclk; m = how many
+__device__ __forceinline__ u64 mvreg_wire_size(const u64 *vclk, unsigned long long V, unsigned long long A, int lane,
+                                               u64 &m) {
+  u64 vsz = 0;
+  m = 0;
+  for (unsigned long long v = 0; v < V; ++v) {
+    const u64 nv = nnz_row(vclk + v * A, A, lane);
+    if (nv) {
+      ++m;
+      vsz += 8 + 12 * nv + 8;
+    }
+  }
+  return vsz;
+}
+
+// Write the register at word k: u64 m, then the occupied slots in slot (Vec) order; returns the next word.
+__device__ inline unsigned long long write_mvreg(uint32_t *w, unsigned long long k, const u64 *vclk, const u64 *vval,
+                                                 unsigned long long V, unsigned long long A, const uint32_t *actors,
+                                                 u64 m, int lane) {
+  if (lane == 0) wr64(w, k, m);
+  k += 2;
+  for (unsigned long long v = 0; v < V; ++v) {
+    const u64 *vr = vclk + v * A;
+    if (nnz_row(vr, A, lane) == 0) continue;
+    k = write_vclock(w, k, vr, A, actors, lane);
+    if (lane == 0) wr64(w, k, vval[v]);
+    k += 2;
+  }
+  return k;
 }
 
 // ---- the walk's frame reader (wire.hip "walk + batched parse"; wire_ops.hip) ----------------------

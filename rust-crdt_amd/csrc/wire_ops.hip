@@ -346,16 +346,6 @@ struct OpsEgressPlan {
   uint32_t *status;
 };
 
-__device__ __forceinline__ u64 wave_excl(u64 v, int lane, u64 &total) {
-  u64 x = v;
-  for (int d = 1; d < kWave; d <<= 1) {
-    const u64 y = __shfl_up(x, d, kWave);
-    if (lane >= d) x += y;
-  }
-  total = __shfl(x, kWave - 1, kWave);
-  return x - v;
-}
-
 // One wave per state, lane = op in batches of 64.  write = 0: validate every op, size the frame
 // (status[s], sizes[s]); write = 1: write it at frame_off[s] (the empty Vec for a state with bit 1).
 template <bool MAP>

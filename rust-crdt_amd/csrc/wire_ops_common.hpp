@@ -1,5 +1,6 @@
 // Shared by the op-stream wire kernels (wire_ops.hip: Orswot and Map<K, MVReg> ops; wire_vmap_ops.hip:
-// the value-typed Maps' ops): the frame walk's reader.
+// the value-typed Maps' ops; wire_mvreg.hip: the standalone MVReg's Puts): the frame walk's reader and
+// the wave prefix sum of the egress.
 #pragma once
 #include "wire_common.hpp"
 
@@ -25,5 +26,17 @@ struct OpWalk : MapWalk<> {
   }
   __device__ u64 at64(unsigned long long k, int lane) { return (u64)at(k, lane) | ((u64)at(k + 1, lane) << 32); }
 };
+
+// Exclusive prefix sum over the wave's lanes (egress: where each op of a batch of 64 starts); total
+// = the wave's sum.
+__device__ __forceinline__ u64 wave_excl(u64 v, int lane, u64 &total) {
+  u64 x = v;
+  for (int d = 1; d < kWave; d <<= 1) {
+    const u64 y = __shfl_up(x, d, kWave);
+    if (lane >= d) x += y;
+  }
+  total = __shfl(x, kWave - 1, kWave);
+  return x - v;
+}
 
 }  // namespace crdt
