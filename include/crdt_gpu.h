@@ -1152,6 +1152,60 @@ int crdt_map_get(crdt_ctx *ctx, const crdt_map_states *states, const uint32_t *s
                  uint64_t *vval /* [Q][V] */, uint32_t *nval /* [Q] */, uint64_t *val_clock /* [Q][A] */,
                  uint32_t *status /* [Q] */);
 
+/* Map::get (map.rs:251-262) and the gotten value's own reads on the value-typed Maps, in their
+ * apply layouts (crdt_map_counter_states / crdt_map_orswot_states / crdt_map_nested_states; Vs / Vd /
+ * Id of 0 mean their defaults, as in the apply calls).  Q queries (state_idx[q], key[q][, member[q] |
+ * ikey[q]]), device u32.  For every get: present[q] = 1 iff the key's ec row is non-zero, rm_clock[q*A ..]
+ * = that row (zeros when absent); add_clock of the outer get is the clock row of state state_idx[q] (the
+ * caller gathers it, as for crdt_map_get).  status[q] bit 1 = a state index, key, member or inner key out
+ * of range: the outputs of an absent element (zeros, present 0).  Outputs marked "or NULL" are skipped
+ * when NULL; every other output element is written on every call.  Q == 0 launches nothing.  Limits
+ * (CRDT_EUNSUPPORTED past them): A <= 512 (the apply calls'), M <= 1,024, K2 <= 256, Vs <= 64.  Device
+ * memory only.
+ *
+ * crdt_map_counter_get — Map<K, GCounter / PNCounter> (W = 1 / 2; ec / val rows at ec + s*ec_stride +
+ *   k*A and val + s*val_stride + (k*W + w)*A): val[(q*W + w)*A ..] = the counter's W rows, zeros when
+ *   absent (V::default()); total[2q] + 2^64·total[2q+1] = GCounter::read (gcounter.rs:70-72) / PNCounter::read
+ *   (pncounter.rs:110-114, P − N in two's complement) of those rows, in the encoding of crdt_gcounter_read /
+ *   crdt_pncounter_read; an absent key reads 0.
+ * crdt_map_orswot_get — Map<K, Orswot<M>>: val_clock[q*A ..] = the key's oc row, the add_clock =
+ *   rm_clock of the gotten set's read() (orswot.rs:264-279); members[q*Mw + w] (Mw = ceil(M/64)) has bit b
+ *   set iff member row 64w + b is non-zero, bits past M 0; len[q] = the bit count; vd_n[q] = the key's
+ *   pending nested removes.  A present key may hold an empty set (present 1, len 0).
+ * crdt_map_orswot_contains — Orswot::contains (orswot.rs:253-262) on the set under key[q]: add_clock =
+ *   the oc row, rm_clock = member[q]'s dot row, val[q] = 1 iff that row is non-zero; under an absent key
+ *   everything is zero (Orswot::default().contains).
+ * crdt_map_nested_get — Map<K, Map<K2, MVReg>>: val_clock = the key's ic row (the inner Map's clock,
+ *   map.rs:301-307), ikeys[q*K2w + w] (K2w = ceil(K2/64)) / len[q] = the inner Map's key set and len
+ *   (map.rs:233-249) from its iec rows, bits past K2 0.
+ * crdt_map_nested_get_inner — the gotten inner Map's get of ikey[q]: add_clock = the ic row, rm_clock =
+ *   the iec row (present[q] = 1 iff it is non-zero), the register = the first nval slots (already in Vec
+ *   order): vclk[(q*Vs + j)*A ..], vval[q*Vs + j], nval[q], the slots past them zero; val_clock = the join
+ *   of those slot clocks (mvreg.rs:207-215).  Under an absent outer or inner key everything is zero.
+ * The member / inner-key scans give each row a power-of-two lane segment, one lane per 16 bytes when A is
+ * even and ent / iec 16-byte aligned (8-byte words otherwise). */
+int crdt_map_counter_get(crdt_ctx *ctx, const crdt_map_counter_states *states, const uint32_t *state_idx,
+                         const uint32_t *key, size_t Q, uint8_t *present /* [Q] */, uint64_t *rm_clock /* [Q][A] */,
+                         uint64_t *val /* [Q][W][A] or NULL */, uint64_t *total /* [Q][2] or NULL */,
+                         uint32_t *status /* [Q] */);
+int crdt_map_orswot_get(crdt_ctx *ctx, const crdt_map_orswot_states *states, const uint32_t *state_idx,
+                        const uint32_t *key, size_t Q, uint8_t *present /* [Q] */, uint64_t *rm_clock /* [Q][A] */,
+                        uint64_t *val_clock /* [Q][A] */, uint64_t *members /* [Q][Mw] */, uint32_t *len /* [Q] */,
+                        uint32_t *vd_n /* [Q] or NULL */, uint32_t *status /* [Q] */);
+int crdt_map_orswot_contains(crdt_ctx *ctx, const crdt_map_orswot_states *states, const uint32_t *state_idx,
+                             const uint32_t *key, const uint32_t *member, size_t Q, uint8_t *val /* [Q] */,
+                             uint64_t *add_clock /* [Q][A] */, uint64_t *rm_clock /* [Q][A] */,
+                             uint32_t *status /* [Q] */);
+int crdt_map_nested_get(crdt_ctx *ctx, const crdt_map_nested_states *states, const uint32_t *state_idx,
+                        const uint32_t *key, size_t Q, uint8_t *present /* [Q] */, uint64_t *rm_clock /* [Q][A] */,
+                        uint64_t *val_clock /* [Q][A] */, uint64_t *ikeys /* [Q][K2w] */, uint32_t *len /* [Q] */,
+                        uint32_t *status /* [Q] */);
+int crdt_map_nested_get_inner(crdt_ctx *ctx, const crdt_map_nested_states *states, const uint32_t *state_idx,
+                              const uint32_t *key, const uint32_t *ikey, size_t Q, uint8_t *present /* [Q] */,
+                              uint64_t *add_clock /* [Q][A] */, uint64_t *rm_clock /* [Q][A] */,
+                              uint64_t *vclk /* [Q][Vs][A] */, uint64_t *vval /* [Q][Vs] */, uint32_t *nval /* [Q] */,
+                              uint64_t *val_clock /* [Q][A] */, uint32_t *status /* [Q] */);
+
 /* ReadCtx::derive_add_ctx (ctx.rs:40-48: dot = add_clock.inc(actor); add_clock.apply(dot)) of Q
  * clock rows: out_clock + q*out_stride = clock + q*clock_stride with [actor[q]] += 1, counter[q] =
  * that new value (the AddCtx's dot is (actor[q], counter[q])).  out_clock may be clock itself

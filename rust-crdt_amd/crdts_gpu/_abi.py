@@ -63,6 +63,8 @@ EXPORTS = (
     "crdt_map_counter_ingest", "crdt_map_counter_egress", "crdt_map_orswot_ingest", "crdt_map_orswot_egress",
     "crdt_orswot_read", "crdt_orswot_contains", "crdt_mvreg_read", "crdt_map_read", "crdt_map_get",
     "crdt_vclock_derive_add",
+    "crdt_map_counter_get", "crdt_map_orswot_get", "crdt_map_orswot_contains", "crdt_map_nested_get",
+    "crdt_map_nested_get_inner",
     "crdt_orswot_ops_ingest", "crdt_map_ops_ingest", "crdt_orswot_ops_egress", "crdt_map_ops_egress",
     "crdt_map_counter_ops_ingest", "crdt_map_orswot_ops_ingest", "crdt_map_nested_ops_ingest",
     "crdt_map_counter_ops_egress", "crdt_map_orswot_ops_egress", "crdt_map_nested_ops_egress",
@@ -417,6 +419,14 @@ _SIGS.update({  # batched ReadCtx queries (csrc/read.hip)
     "crdt_mvreg_read": ([P, ctypes.POINTER(MVRegStates), P, S, P, P], ctypes.c_int),
     "crdt_map_get": ([P, ctypes.POINTER(MapStates), P, P, S, P, P, P, P, P, P, P], ctypes.c_int),
     "crdt_vclock_derive_add": ([P, P, S, S, S, P, P, S, P, P], ctypes.c_int),
+})
+_SIGS.update({  # the same on the value-typed Maps (csrc/read_vmap.hip)
+    "crdt_map_counter_get": ([P, ctypes.POINTER(MapCounterStates), P, P, S, P, P, P, P, P], ctypes.c_int),
+    "crdt_map_orswot_get": ([P, ctypes.POINTER(MapOrswotStates), P, P, S, P, P, P, P, P, P, P], ctypes.c_int),
+    "crdt_map_orswot_contains": ([P, ctypes.POINTER(MapOrswotStates), P, P, P, S, P, P, P, P], ctypes.c_int),
+    "crdt_map_nested_get": ([P, ctypes.POINTER(MapNestedStates), P, P, S, P, P, P, P, P, P], ctypes.c_int),
+    "crdt_map_nested_get_inner": ([P, ctypes.POINTER(MapNestedStates), P, P, P, S, P, P, P, P, P, P, P, P],
+                                  ctypes.c_int),
 })
 _SIGS.update({  # op streams on the wire (csrc/wire_ops.hip)
     "crdt_orswot_ops_ingest": ([P, P, P, S, P, S, P, S, ctypes.POINTER(OrswotOpsBuf), P, P, P,

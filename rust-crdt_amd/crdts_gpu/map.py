@@ -1452,3 +1452,353 @@ def get(states, state_idx: torch.Tensor, key: torch.Tensor, ctx: Optional[Contex
              status.data_ptr())
     return (_rc.ReadCtx(_rc.gather_rows(ctx, clock, state_idx), rm_clock,
                         MapGetVal(present, oclk, oval, nval, val_clock)), status)
+
+
+# ---------------------------------------------------------------------------------------------
+# Batched reads of the value-typed Maps: Map::get with the gotten value's own read
+# (crdt_map_{counter,orswot,nested}_get, crdt_map_orswot_contains, crdt_map_nested_get_inner;
+# csrc/read_vmap.hip), and the whole-state reads as compositions of the presence scans
+# ---------------------------------------------------------------------------------------------
+class MapCounterGetVal(NamedTuple):
+    """val of map.counter_get."""
+    present: torch.Tensor  # (Q,) uint8: the key has an entry (Map::get -> Some)
+    val: torch.Tensor      # (Q, W, A): the counter's rows (GCounter: W = 1; PNCounter: P, N), zeros when absent
+    total: torch.Tensor    # (Q, 2): GCounter / PNCounter::read as lo, hi words (two's complement)
+
+
+class MapOrswotGetVal(NamedTuple):
+    """val of map.orswot_get: the gotten set's read()."""
+    present: torch.Tensor    # (Q,) uint8
+    val_clock: torch.Tensor  # (Q, A): the set's clock (add_clock = rm_clock of its read())
+    members: torch.Tensor    # (Q, Mw) int64 bitmap
+    len: torch.Tensor        # (Q,) int32
+    vd_n: torch.Tensor       # (Q,) int32: the key's pending nested removes
+
+
+class MapNestedGetVal(NamedTuple):
+    """val of map.nested_get: the gotten inner Map's key set and len."""
+    present: torch.Tensor    # (Q,) uint8
+    val_clock: torch.Tensor  # (Q, A): the inner Map's clock
+    ikeys: torch.Tensor      # (Q, K2w) int64 bitmap
+    len: torch.Tensor        # (Q,) int32
+
+
+class MapCounterReadVal(NamedTuple):
+    keys: torch.Tensor   # (N, Kw) int64 bitmap
+    len: torch.Tensor    # (N,) int32
+    total: torch.Tensor  # (N, K, 2): every key's counter read as lo, hi words (0 when absent)
+
+
+class MapOrswotReadVal(NamedTuple):
+    keys: torch.Tensor     # (N, Kw) int64 bitmap
+    len: torch.Tensor      # (N,) int32
+    members: torch.Tensor  # (N, K, Mw) int64 bitmaps of every key's set
+    lens: torch.Tensor     # (N, K) int32
+
+
+class MapNestedReadVal(NamedTuple):
+    keys: torch.Tensor   # (N, Kw) int64 bitmap
+    len: torch.Tensor    # (N,) int32
+    ikeys: torch.Tensor  # (N, K, K2w) int64 bitmaps of every key's inner Map
+    lens: torch.Tensor   # (N, K) int32
+
+
+def _check_read_args(what: str, rows, counts, index) -> None:
+    """check_args plus the states' int32 count tensors (vd_n, nval): every dtype and layout first,
+    then every device, all ValueError before a Context exists."""
+    for t, nm in counts:
+        if not isinstance(t, torch.Tensor) or t.dtype not in _rc.U32_DTYPES:
+            raise ValueError(f"{what}({nm}): dtype {getattr(t, 'dtype', type(t))}; expected one of {_rc.U32_DTYPES}")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}({nm}): must be contiguous")
+    _rc.check_args(what, rows, index)
+    for t, nm in counts:
+        if t.device.type != "cuda":
+            raise ValueError(f"{what}({nm}): tensor on {t.device}; expected a cuda tensor")
+    Q = index[0][0].shape[0] if index else 0
+    for t, nm in index:
+        if t.shape[0] != Q:
+            raise ValueError(f"{what}: {index[0][1]} and {nm} differ in length")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}({nm}): the query vector must be contiguous")
+
+
+def _read_ctx_tensors(ctx: Context, what: str, rows, counts, index) -> None:
+    for t, nm in rows:
+        ctx.check_tensor(t, f"{what}({nm})")
+    for t, nm in tuple(counts) + tuple(index):
+        ctx.check_tensor(t, f"{what}({nm})", _rc.U32_DTYPES)
+
+
+def _counter_read_states(what: str, states):
+    clock, ec, val = states.clock, states.ec, states.val
+    if clock.dim() != 2 or ec.dim() != 3 or val.dim() != 4:
+        raise ValueError(f"{what}: clock (N, A), ec (N, K, A), val (N, K, W, A) expected")
+    N, A = clock.shape
+    K, W = val.shape[1], val.shape[2]
+    if (tuple(ec.shape) != (N, K, A) or tuple(val.shape) != (N, K, W, A) or W not in (1, 2)
+            or (K > 1 and ec.stride(1) != A) or (W > 1 and val.stride(2) != A) or (K > 1 and val.stride(1) != W * A)
+            or (N > 1 and (ec.stride(0) < K * A or val.stride(0) < K * W * A))):
+        raise ValueError(f"{what}: per-state blocks must be packed (K, A) / (K, W, A), W = 1 or 2")
+    return N, K, A, W
+
+
+def counter_get(states, state_idx: torch.Tensor, key: torch.Tensor, ctx: Optional[Context] = None):
+    """Map::get (map.rs:251-262) of Q queries (state_idx[q], key[q]) ((Q,) int32 device tensors) on
+    Map<K, GCounter / PNCounter> states, with the gotten counter's read() (gcounter.rs:70-72 /
+    pncounter.rs:110-114): `states` a MapCounterLub or anything with its clock (N, A) / ec (N, K, A) / val
+    (N, K, W, A) tensors (strided over states allowed).  Returns (ReadCtx(add_clock (Q, A) = the queried
+    states' clocks, rm_clock (Q, A) = the entry clocks, zeros when absent, val = MapCounterGetVal), status
+    (Q,) int32: bit 1 = state index or key out of range).  An absent key reads as the default counter:
+    zero rows, total 0.
+
+    The dot of the counter's own inc / dec needs no further call: it is derive_add_ctx over the gotten
+    P (inc) or N (dec) row, ReadCtx(val.val[:, dir, :], ...), with the value actor — GCounter::inc is
+    inner.inc(actor) (gcounter.rs:62-64) — and an absent key gives counter 1."""
+    what = "map.counter_get"
+    rows = [(states.clock, "clock"), (states.ec, "ec"), (states.val, "val")]
+    index = [(state_idx, "state_idx"), (key, "key")]
+    _check_read_args(what, rows, [], index)
+    N, K, A, W = _counter_read_states(what, states)
+    clock, ec, val = states.clock, states.ec, states.val
+    ctx = ctx or Context.default(clock.device.index)
+    _read_ctx_tensors(ctx, what, rows, [], index)
+    st = _abi.MapCounterStates()
+    st.N, st.K, st.A, st.W = N, K, A, W
+    st.clock, st.clock_stride = clock.data_ptr(), clock.stride(0) if N > 1 else A
+    st.ec, st.ec_stride = ec.data_ptr(), ec.stride(0) if N > 1 else K * A
+    st.val, st.val_stride = val.data_ptr(), val.stride(0) if N > 1 else K * W * A
+    Q, dev = state_idx.shape[0], clock.device
+    present = torch.empty(Q, dtype=torch.uint8, device=dev)
+    rm_clock = torch.empty((Q, A), dtype=clock.dtype, device=dev)
+    oval = torch.empty((Q, W, A), dtype=val.dtype, device=dev)
+    total = torch.empty((Q, 2), dtype=val.dtype, device=dev)
+    status = torch.empty(Q, dtype=torch.int32, device=dev)
+    ctx.call("crdt_map_counter_get", ctypes.byref(st), state_idx.data_ptr(), key.data_ptr(), Q, present.data_ptr(),
+             rm_clock.data_ptr(), oval.data_ptr(), total.data_ptr(), status.data_ptr())
+    return (_rc.ReadCtx(_rc.gather_rows(ctx, clock, state_idx), rm_clock, MapCounterGetVal(present, oval, total)),
+            status)
+
+
+def _orswot_read_states(what: str, states, index, vd: bool):
+    """-> (rows, counts) checked, and the crdt_map_orswot_states dims (N, K, M, A)."""
+    rows = [(states.clock, "clock"), (states.ec, "ec"), (states.oc, "oc"), (states.ent, "ent")]
+    counts = [(states.vd_n, "vd_n")] if vd else []
+    _check_read_args(what, rows, counts, index)
+    clock, ec, oc, ent = states.clock, states.ec, states.oc, states.ent
+    if clock.dim() != 2 or ent.dim() != 4:
+        raise ValueError(f"{what}: clock (N, A), ec / oc (N, K, A), ent (N, K, M, A) expected")
+    N, A = clock.shape
+    K, M = ent.shape[1], ent.shape[2]
+    if tuple(ec.shape) != (N, K, A) or tuple(oc.shape) != (N, K, A) or tuple(ent.shape) != (N, K, M, A):
+        raise ValueError(f"{what}: shapes clock {tuple(clock.shape)} ec {tuple(ec.shape)} oc {tuple(oc.shape)} "
+                         f"ent {tuple(ent.shape)} do not agree")
+    for t, nm in rows[1:]:
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: {nm} must be packed (contiguous)")
+    if clock.stride(0) != A and N > 1:
+        raise ValueError(f"{what}: clock must be packed (contiguous)")
+    if vd and tuple(states.vd_n.shape) != (N, K):
+        raise ValueError(f"{what}: vd_n must be an (N, K) int32 tensor")
+    return rows, counts, (N, K, M, A)
+
+
+def _orswot_struct(states, dims, vd: bool):
+    N, K, M, A = dims
+    st = _abi.MapOrswotStates()
+    st.N, st.K, st.M, st.A = N, K, M, A
+    st.clock, st.ec, st.oc, st.ent = (states.clock.data_ptr(), states.ec.data_ptr(), states.oc.data_ptr(),
+                                      states.ent.data_ptr())
+    if vd:
+        st.vd_n = states.vd_n.data_ptr()
+    return st
+
+
+def orswot_get(states, state_idx: torch.Tensor, key: torch.Tensor, ctx: Optional[Context] = None):
+    """Map::get (map.rs:251-262) of Q queries (state_idx[q], key[q]) on Map<K, Orswot<M>> states, with the
+    gotten set's read() (orswot.rs:264-279): `states` a MapOrswotLub (G = N) or anything with its clock /
+    ec / oc / ent / vd_n tensors.  Returns (ReadCtx(add_clock = the queried states' clocks, rm_clock = the
+    entry clocks, val = MapOrswotGetVal), status (Q,) int32).  A present key may hold an empty set."""
+    what = "map.orswot_get"
+    index = [(state_idx, "state_idx"), (key, "key")]
+    rows, counts, dims = _orswot_read_states(what, states, index, True)
+    N, K, M, A = dims
+    ctx = ctx or Context.default(states.clock.device.index)
+    _read_ctx_tensors(ctx, what, rows, counts, index)
+    st = _orswot_struct(states, dims, True)
+    Q, dev, Mw = state_idx.shape[0], states.clock.device, (M + 63) // 64
+    present = torch.empty(Q, dtype=torch.uint8, device=dev)
+    rm_clock = torch.empty((Q, A), dtype=states.clock.dtype, device=dev)
+    val_clock = torch.empty((Q, A), dtype=states.clock.dtype, device=dev)
+    members = torch.empty((Q, Mw), dtype=torch.int64, device=dev)
+    n = torch.empty(Q, dtype=torch.int32, device=dev)
+    vd_n = torch.empty(Q, dtype=torch.int32, device=dev)
+    status = torch.empty(Q, dtype=torch.int32, device=dev)
+    ctx.call("crdt_map_orswot_get", ctypes.byref(st), state_idx.data_ptr(), key.data_ptr(), Q, present.data_ptr(),
+             rm_clock.data_ptr(), val_clock.data_ptr(), members.data_ptr(), n.data_ptr(), vd_n.data_ptr(),
+             status.data_ptr())
+    return (_rc.ReadCtx(_rc.gather_rows(ctx, states.clock, state_idx), rm_clock,
+                        MapOrswotGetVal(present, val_clock, members, n, vd_n)), status)
+
+
+def orswot_contains(states, state_idx: torch.Tensor, key: torch.Tensor, member: torch.Tensor,
+                    ctx: Optional[Context] = None):
+    """Orswot::contains (orswot.rs:253-262) of member[q] on the set under (state_idx[q], key[q]).  Returns
+    (ReadCtx(add_clock (Q, A) = the set's clock (the oc row), rm_clock (Q, A) = the member's dot clock,
+    val (Q,) uint8), status (Q,) int32) — the nested value's own ReadCtx, whose derive_rm_ctx builds the
+    nested Rm.  Under an absent key everything is zero (Orswot::default().contains)."""
+    what = "map.orswot_contains"
+    index = [(state_idx, "state_idx"), (key, "key"), (member, "member")]
+    rows, counts, dims = _orswot_read_states(what, states, index, False)
+    N, K, M, A = dims
+    ctx = ctx or Context.default(states.clock.device.index)
+    _read_ctx_tensors(ctx, what, rows, counts, index)
+    st = _orswot_struct(states, dims, False)
+    Q, dev = state_idx.shape[0], states.clock.device
+    val = torch.empty(Q, dtype=torch.uint8, device=dev)
+    add_clock = torch.empty((Q, A), dtype=states.clock.dtype, device=dev)
+    rm_clock = torch.empty((Q, A), dtype=states.clock.dtype, device=dev)
+    status = torch.empty(Q, dtype=torch.int32, device=dev)
+    ctx.call("crdt_map_orswot_contains", ctypes.byref(st), state_idx.data_ptr(), key.data_ptr(), member.data_ptr(), Q,
+             val.data_ptr(), add_clock.data_ptr(), rm_clock.data_ptr(), status.data_ptr())
+    return _rc.ReadCtx(add_clock, rm_clock, val), status
+
+
+def _nested_read_states(what: str, states, index, regs: bool):
+    rows = [(states.clock, "clock"), (states.ec, "ec"), (states.ic, "ic"), (states.iec, "iec")]
+    counts = []
+    if regs:
+        rows += [(states.ivc, "ivc"), (states.ivv, "ivv")]
+        counts = [(states.nval, "nval")]
+    _check_read_args(what, rows, counts, index)
+    clock, iec = states.clock, states.iec
+    if clock.dim() != 2 or iec.dim() != 4:
+        raise ValueError(f"{what}: clock (N, A), ec / ic (N, K, A), iec (N, K, K2, A) expected")
+    N, A = clock.shape
+    K, K2 = iec.shape[1], iec.shape[2]
+    shapes = dict(ec=(N, K, A), ic=(N, K, A), iec=(N, K, K2, A))
+    Vs = 0
+    if regs:
+        Vs = states.ivc.shape[3] if states.ivc.dim() == 5 else -1
+        if not 1 <= Vs <= 64:
+            raise ValueError(f"{what}: ivc (N, K, K2, Vs, A) with Vs in 1..64 expected")
+        shapes.update(ivc=(N, K, K2, Vs, A), ivv=(N, K, K2, Vs), nval=(N, K, K2))
+    for nm, shp in shapes.items():
+        t = getattr(states, nm)
+        if tuple(t.shape) != shp or not t.is_contiguous():
+            raise ValueError(f"{what}: {nm} must be a packed (contiguous) {shp} tensor")
+    if clock.stride(0) != A and N > 1:
+        raise ValueError(f"{what}: clock must be packed (contiguous)")
+    return rows, counts, (N, K, K2, A, Vs)
+
+
+def _nested_struct(states, dims, regs: bool):
+    st = _abi.MapNestedStates()
+    st.N, st.K, st.K2, st.A, st.Vs = dims
+    for nm in ("clock", "ec", "ic", "iec") + (("ivc", "ivv", "nval") if regs else ()):
+        setattr(st, nm, getattr(states, nm).data_ptr())
+    return st
+
+
+def nested_get(states, state_idx: torch.Tensor, key: torch.Tensor, ctx: Optional[Context] = None):
+    """Map::get (map.rs:251-262) of Q queries (state_idx[q], key[q]) on Map<K, Map<K2, MVReg>> states, with
+    the gotten inner Map's len / key set (map.rs:233-249): `states` a MapNestedLub (G = N) or anything with
+    its clock / ec / ic / iec tensors.  Returns (ReadCtx(add_clock = the queried states' clocks, rm_clock =
+    the entry clocks, val = MapNestedGetVal), status (Q,) int32).  The one context derived from it runs
+    through every level of an update, as in the reference's tests (test/map.rs)."""
+    what = "map.nested_get"
+    index = [(state_idx, "state_idx"), (key, "key")]
+    rows, counts, dims = _nested_read_states(what, states, index, False)
+    N, K, K2, A, _ = dims
+    ctx = ctx or Context.default(states.clock.device.index)
+    _read_ctx_tensors(ctx, what, rows, counts, index)
+    st = _nested_struct(states, dims, False)
+    Q, dev, K2w = state_idx.shape[0], states.clock.device, (K2 + 63) // 64
+    present = torch.empty(Q, dtype=torch.uint8, device=dev)
+    rm_clock = torch.empty((Q, A), dtype=states.clock.dtype, device=dev)
+    val_clock = torch.empty((Q, A), dtype=states.clock.dtype, device=dev)
+    ikeys = torch.empty((Q, K2w), dtype=torch.int64, device=dev)
+    n = torch.empty(Q, dtype=torch.int32, device=dev)
+    status = torch.empty(Q, dtype=torch.int32, device=dev)
+    ctx.call("crdt_map_nested_get", ctypes.byref(st), state_idx.data_ptr(), key.data_ptr(), Q, present.data_ptr(),
+             rm_clock.data_ptr(), val_clock.data_ptr(), ikeys.data_ptr(), n.data_ptr(), status.data_ptr())
+    return (_rc.ReadCtx(_rc.gather_rows(ctx, states.clock, state_idx), rm_clock,
+                        MapNestedGetVal(present, val_clock, ikeys, n)), status)
+
+
+def nested_get_inner(states, state_idx: torch.Tensor, key: torch.Tensor, ikey: torch.Tensor,
+                     ctx: Optional[Context] = None):
+    """The gotten inner Map's get of ikey[q] under (state_idx[q], key[q]).  Returns (ReadCtx(add_clock (Q, A)
+    = the inner Map's clock (the ic row), rm_clock (Q, A) = the inner entry clock, val = MapGetVal: the
+    register's values in Vec order and the join of their clocks), status (Q,) int32) — the inner Map's own
+    ReadCtx, whose derive_rm_ctx builds the inner Rm.  Under an absent outer or inner key everything is zero."""
+    what = "map.nested_get_inner"
+    index = [(state_idx, "state_idx"), (key, "key"), (ikey, "ikey")]
+    rows, counts, dims = _nested_read_states(what, states, index, True)
+    N, K, K2, A, Vs = dims
+    ctx = ctx or Context.default(states.clock.device.index)
+    _read_ctx_tensors(ctx, what, rows, counts, index)
+    st = _nested_struct(states, dims, True)
+    Q, dev = state_idx.shape[0], states.clock.device
+    present = torch.empty(Q, dtype=torch.uint8, device=dev)
+    add_clock = torch.empty((Q, A), dtype=states.clock.dtype, device=dev)
+    rm_clock = torch.empty((Q, A), dtype=states.clock.dtype, device=dev)
+    vclk = torch.empty((Q, Vs, A), dtype=states.ivc.dtype, device=dev)
+    vval = torch.empty((Q, Vs), dtype=states.ivv.dtype, device=dev)
+    nval = torch.empty(Q, dtype=torch.int32, device=dev)
+    val_clock = torch.empty((Q, A), dtype=states.clock.dtype, device=dev)
+    status = torch.empty(Q, dtype=torch.int32, device=dev)
+    ctx.call("crdt_map_nested_get_inner", ctypes.byref(st), state_idx.data_ptr(), key.data_ptr(), ikey.data_ptr(), Q,
+             present.data_ptr(), add_clock.data_ptr(), rm_clock.data_ptr(), vclk.data_ptr(), vval.data_ptr(),
+             nval.data_ptr(), val_clock.data_ptr(), status.data_ptr())
+    return _rc.ReadCtx(add_clock, rm_clock, MapGetVal(present, vclk, vval, nval, val_clock)), status
+
+
+def counter_read(states, ctx: Optional[Context] = None) -> "_rc.ReadCtx":
+    """Map::len / read_ctx (map.rs:233-249, :301-307) of N Map<K, GCounter / PNCounter> states with every
+    key's counter read: ReadCtx(clock, clock, MapCounterReadVal(keys, len, total (N, K, 2))).  A composition
+    of crdt_map_read and crdt_gcounter_read / crdt_pncounter_read over the N*K value rows, so `val` must be
+    packed (contiguous); ValueError otherwise."""
+    what = "map.counter_read"
+    rows = [(states.clock, "clock"), (states.ec, "ec"), (states.val, "val")]
+    _check_read_args(what, rows, [], [])
+    N, K, A, W = _counter_read_states(what, states)
+    if not states.val.is_contiguous():
+        raise ValueError(f"{what}: val must be packed (contiguous): its N*K value rows are read as one array")
+    ctx = ctx or Context.default(states.clock.device.index)
+    _read_ctx_tensors(ctx, what, rows, [], [])
+    rc = read(states.clock, states.ec, ctx=ctx)
+    total = torch.empty((N, K, 2), dtype=states.val.dtype, device=states.clock.device)
+    ctx.call("crdt_gcounter_read" if W == 1 else "crdt_pncounter_read", states.val.data_ptr(), N * K, A, W * A,
+             total.data_ptr())
+    return _rc.ReadCtx(states.clock, states.clock, MapCounterReadVal(rc.val[0], rc.val[1], total))
+
+
+def orswot_read(res, ctx: Optional[Context] = None) -> "_rc.ReadCtx":
+    """Map::len / read_ctx of N Map<K, Orswot<M>> states with every key's member set:
+    ReadCtx(clock, clock, MapOrswotReadVal(keys, len, members (N, K, Mw), lens (N, K))) — crdt_map_read over
+    ec and crdt_orswot_read over ent seen as N*K sets (an absent key's member rows are zero)."""
+    what = "map.orswot_read"
+    rows, _, (N, K, M, A) = _orswot_read_states(what, res, [], False)
+    ctx = ctx or Context.default(res.clock.device.index)
+    _read_ctx_tensors(ctx, what, rows, [], [])
+    rc = read(res.clock, res.ec, ctx=ctx)
+    members = torch.empty((N, K, (M + 63) // 64), dtype=torch.int64, device=res.clock.device)
+    lens = torch.empty((N, K), dtype=torch.int32, device=res.clock.device)
+    ctx.call("crdt_orswot_read", res.ent.data_ptr(), A, M * A, N * K, M, A, members.data_ptr(), lens.data_ptr())
+    return _rc.ReadCtx(res.clock, res.clock, MapOrswotReadVal(rc.val[0], rc.val[1], members, lens))
+
+
+def nested_read(res, ctx: Optional[Context] = None) -> "_rc.ReadCtx":
+    """Map::len / read_ctx of N Map<K, Map<K2, MVReg>> states with every key's inner key set:
+    ReadCtx(clock, clock, MapNestedReadVal(keys, len, ikeys (N, K, K2w), lens (N, K))) — crdt_map_read over
+    ec and over iec seen as N*K maps."""
+    what = "map.nested_read"
+    rows, _, (N, K, K2, A, _) = _nested_read_states(what, res, [], False)
+    ctx = ctx or Context.default(res.clock.device.index)
+    _read_ctx_tensors(ctx, what, rows, [], [])
+    rc = read(res.clock, res.ec, ctx=ctx)
+    ikeys = torch.empty((N, K, (K2 + 63) // 64), dtype=torch.int64, device=res.clock.device)
+    lens = torch.empty((N, K), dtype=torch.int32, device=res.clock.device)
+    ctx.call("crdt_map_read", res.iec.data_ptr(), A, K2 * A, N * K, K2, A, ikeys.data_ptr(), lens.data_ptr())
+    return _rc.ReadCtx(res.clock, res.clock, MapNestedReadVal(rc.val[0], rc.val[1], ikeys, lens))

@@ -9,6 +9,9 @@ tensors of dense rows, one per state or query, and `val` is what the read comput
     mvreg.read       val = (vals (N, V) int64 compacted in Vec order, nval (N,) int32)
     map.read         val = (keys (N, Kw) int64 bitmap, len (N,) int32)
     map.get          val = MapGetVal(present, vclk, vval, nval, val_clock)
+    map.counter_get / orswot_get / nested_get      val = MapCounterGetVal / MapOrswotGetVal / MapNestedGetVal
+    map.orswot_contains / nested_get_inner         the nested value's own ReadCtx (val (Q,) uint8 / MapGetVal)
+    map.counter_read / orswot_read / nested_read   val = keys, len and every key's total / members / inner keys
 
 so read -> derive ctx -> op -> apply_batch stays on the device (include/crdt_gpu.h "batched
 ReadCtx queries").  Nothing here synchronises with the host.

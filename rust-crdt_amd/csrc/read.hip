@@ -4,6 +4,7 @@
 // The presence scan (a member / key is present <=> its dot-clock row is non-zero) is a read-only
 // stream over the whole entry array; the gathers touch a few rows per query.
 #include "common.hpp"
+#include "read_common.hpp"
 
 namespace crdt {
 
@@ -162,36 +163,8 @@ static int presence_scan(crdt_ctx *ctx, const char *what, const uint64_t *in, si
   return CRDT_OK;
 }
 
-// ---- gathers: one wave per query / register -------------------------------------------------
-#define QUERY_WAVE_LOOP(Q)                                                                          \
-  const int lane = threadIdx.x % kWave;                                                             \
-  const unsigned long long w0 = (blockIdx.x * (unsigned long long)kBlock + threadIdx.x) / kWave;   \
-  const unsigned long long nw = (unsigned long long)gridDim.x * (kBlock / kWave);                   \
-  for (unsigned long long q = w0; q < (Q); q += nw)
-
-static unsigned query_grid(const crdt_ctx *ctx, unsigned long long Q) {
-  const unsigned long long want = (Q + kBlock / kWave - 1) / (kBlock / kWave);
-  const unsigned long long cap = (unsigned long long)ctx->cu_count * 8;
-  return (unsigned)(want < cap ? want : cap);
-}
-
-// dst[0..A) = src ? src[0..A) : 0; returns (wave-uniform) whether any copied word is non-zero.
-__device__ __forceinline__ bool copy_row(u64 *dst, const u64 *src, unsigned long long A, int lane) {
-  bool nz = false;
-  for (unsigned long long a = lane; a < A; a += kWave) {
-    const u64 v = src ? src[a] : 0;
-    dst[a] = v;
-    nz |= v != 0;
-  }
-  return __ballot(nz) != 0;
-}
-
-__device__ __forceinline__ bool row_nonzero(const u64 *src, unsigned long long A, int lane) {
-  bool nz = false;
-  for (unsigned long long a = lane; a < A; a += kWave) nz |= src[a] != 0;
-  return __ballot(nz) != 0;
-}
-
+// ---- gathers: one wave per query / register (QUERY_WAVE_LOOP, query_grid, copy_row and
+// row_nonzero: read_common.hpp) ---------------------------------------------------------------
 struct ContainsPlan {
   const u64 *entries;
   unsigned long long mstride, sstride, N, M, A, Q;
