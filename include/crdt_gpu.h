@@ -193,6 +193,30 @@ int crdt_lwwreg_merge_batch(crdt_ctx *ctx, uint64_t *self_marker, uint64_t *self
                             const uint64_t *other_marker, const uint64_t *other_val,
                             size_t N, uint8_t *conflict);
 
+/* Batched FunkyCmRDT::apply of LWWReg (lwwreg.rs:48-57: the op is a whole register, applied through
+ * update, :84-98).  Register i applies ops [op_off[i], op_off[i+1]) in order: a larger marker
+ * replaces the state, an equal marker with a different value is Err(ConflictingMarker) and leaves
+ * it unchanged, anything else is a no-op.  Markers compare as unsigned 64-bit over the full range.
+ * Streams are ragged; an empty range leaves the register bit-identical.
+ * conflict[o] (device u8, may be NULL) = 1 where op o returned Err, else 0; written for every op of
+ * every register with a valid range.  status[i] (device u32, may be NULL; written for every i):
+ * bit 0 = some op of the register returned Err; bit 3 = op_off[i] > op_off[i+1] or op_off[i+1] >
+ * n_ops: the register is untouched and its conflict bytes are not written.  As in
+ * crdt_mvreg_apply_batch a register with a valid range of its own is applied over that range
+ * whatever its neighbours' offsets are; where two registers' ranges overlap, the conflict byte of an
+ * op in both is unspecified.  Device memory only.  One wave per 64 registers, a segmented scan over
+ * their contiguous op range (csrc/lwwreg_apply.hip). */
+typedef struct crdt_lwwreg_ops {
+  size_t n_ops;
+  const uint64_t *op_off;  /* [N+1]   */
+  const uint64_t *marker;  /* [n_ops] */
+  const uint64_t *val;     /* [n_ops] */
+} crdt_lwwreg_ops;
+
+int crdt_lwwreg_apply_batch(crdt_ctx *ctx, uint64_t *marker /* [N] */, uint64_t *val /* [N] */, size_t N,
+                            const crdt_lwwreg_ops *ops, uint8_t *conflict /* [n_ops] or NULL */,
+                            uint32_t *status /* [N] or NULL */);
+
 /* ---- Orswot<member, actor> ---------------------------------------------------------------
  * Replaces Orswot::merge (orswot.rs:81-149) incl. apply_rm (:230-250) and apply_deferred
  * (:281-286).
@@ -1630,6 +1654,83 @@ int crdt_mvreg_ops_ingest(crdt_ctx *ctx, const uint8_t *bytes, const uint64_t *f
                           uint64_t *totals);
 int crdt_mvreg_ops_egress(crdt_ctx *ctx, const crdt_mvreg_ops *ops, size_t N, const uint32_t *actors, size_t A,
                           uint64_t *frame_off, uint8_t *bytes, size_t cap, size_t *total, uint32_t *status);
+
+/* ---- serde wire format of the lattice types' op streams ----------------------------------------------
+ * The ops of VClock / GCounter, PNCounter, GSet and LWWReg derive serde too; every record is
+ * fixed-width, so a frame is exactly 8 + n x rec bytes:
+ *   Vec<Dot<u32>>           = u64 n, n x (u32 actor, u64 counter)            rec 12  (vclock.rs:32-38)
+ *   Vec<pncounter::Op<u32>> = u64 n, n x (u32 actor, u64 counter, u32 dir)   rec 16  (pncounter.rs:35-51)
+ *   Vec<u64>                = u64 n, n x u64 element                         rec 8   (gset.rs:43-49)
+ *   Vec<LWWReg<u64, u64>>   = u64 n, n x (u64 val, u64 marker)               rec 16  (lwwreg.rs:13-19, :52)
+ * dir: 0 = Pos, 1 = Neg.  GCounter's op is the same Dot (gcounter.rs:36-42): its streams go through
+ * the vclock calls.  e.g. (as 32-bit words) Vec[Dot(7, 3)] = 1 0 | 7 3 0; Vec[Op { dot: (7, 3), dir: Neg }] = 1 0 | 7 3 0 1;
+ * Vec[LWWReg { val: 10, marker: 2 }] = 1 0 | 10 0 | 2 0.
+ * The contract is the one stated for crdt_orswot_ops_ingest, restricted to ops (no rows, no ids): the
+ * frames, the sorted unique dictionaries (actors u32; elems u64, the GSet universe; none for LWWReg),
+ * the status bits, totals, the sizing call, the no-sync path and the prefix cut.  Ingest fills a
+ * crdt_dot_ops_buf / crdt_lwwreg_ops_buf, the mutable twin of crdt_dot_ops / crdt_lwwreg_ops with the
+ * same field order and sizes and op_cap where the const struct holds n_ops, so a filled buffer casts
+ * to the const struct.  crdt_dot_ops is what crdt_vclock / gcounter / pncounter / gset_apply_batch
+ * take (state_idx, actor or element, counter, dir), grouped by state: ops in frame order, states in
+ * order, state_idx[o] = the frame's index, op_off (N+1) written; GSet leaves counter and dir alone
+ * (may be NULL), VClock dir.  Every element of the first n_ops entries is written by the call.
+ * totals (host, may be NULL) = {ops}.  Records are fixed-width, so ops <= (B_s - 8) / rec is an exact
+ * bound for a well-formed frame of B_s bytes: a caller can size op_cap without a sync from frame_off
+ * alone.
+ * status[s] (device u32, written for every s): bit 0 = malformed (a misaligned offset, a frame
+ * shorter than 8 bytes, a length other than 8 + n x rec, a dir tag other than 0 / 1): no ops, no
+ * neighbour's offsets shifted; bit 1 = an actor / element missing from its dictionary: written as
+ * 0xFFFFFFFF, the op keeps its place (the apply kernels skip it and count it into bad); bit 2 =
+ * capacity (the prefix cut; nothing is written past op_cap).
+ * Egress reads the grouped form (op_off and the arrays, never state_idx) with the sizing protocol of
+ * crdt_orswot_egress.  status[s] bit 1 = the state has an op with no wire form (an index >= A / U, a
+ * dir > 1, an invalid op_off): its frame is the empty Vec.  Ingest -> egress is byte-identical for
+ * well-formed frames whose ids are all in the dictionaries.  Device pointers only.  No limit on A / U
+ * (a dictionary past 48 KiB is searched in global memory instead of LDS); N <= 2^32 - 1. */
+typedef struct crdt_dot_ops {
+  size_t n_ops;
+  const uint64_t *op_off;    /* [N+1]                                    */
+  const uint32_t *state_idx; /* [n_ops]                                  */
+  const uint32_t *actor;     /* [n_ops]  (GSet: the dense element index) */
+  const uint64_t *counter;   /* [n_ops]  (GSet: NULL)                    */
+  const uint8_t *dir;        /* [n_ops]  (PNCounter only, else NULL)     */
+} crdt_dot_ops;
+
+typedef struct crdt_dot_ops_buf { /* mutable twin of crdt_dot_ops: same field order and sizes */
+  size_t op_cap;
+  uint64_t *op_off;    /* [N+1]    */
+  uint32_t *state_idx; /* [op_cap] */
+  uint32_t *actor;     /* [op_cap] */
+  uint64_t *counter;   /* [op_cap] */
+  uint8_t *dir;        /* [op_cap] */
+} crdt_dot_ops_buf;
+
+typedef struct crdt_lwwreg_ops_buf { /* mutable twin of crdt_lwwreg_ops: same field order and sizes */
+  size_t op_cap;
+  uint64_t *op_off; /* [N+1]    */
+  uint64_t *marker; /* [op_cap] */
+  uint64_t *val;    /* [op_cap] */
+} crdt_lwwreg_ops_buf;
+
+int crdt_vclock_ops_ingest(crdt_ctx *ctx, const uint8_t *bytes, const uint64_t *frame_off, size_t N,
+                           const uint32_t *actors, size_t A, const crdt_dot_ops_buf *out, uint32_t *status,
+                           uint64_t *totals);
+int crdt_pncounter_ops_ingest(crdt_ctx *ctx, const uint8_t *bytes, const uint64_t *frame_off, size_t N,
+                              const uint32_t *actors, size_t A, const crdt_dot_ops_buf *out, uint32_t *status,
+                              uint64_t *totals);
+int crdt_gset_ops_ingest(crdt_ctx *ctx, const uint8_t *bytes, const uint64_t *frame_off, size_t N,
+                         const uint64_t *elems, size_t U, const crdt_dot_ops_buf *out, uint32_t *status,
+                         uint64_t *totals);
+int crdt_lwwreg_ops_ingest(crdt_ctx *ctx, const uint8_t *bytes, const uint64_t *frame_off, size_t N,
+                           const crdt_lwwreg_ops_buf *out, uint32_t *status, uint64_t *totals);
+int crdt_vclock_ops_egress(crdt_ctx *ctx, const crdt_dot_ops *ops, size_t N, const uint32_t *actors, size_t A,
+                           uint64_t *frame_off, uint8_t *bytes, size_t cap, size_t *total, uint32_t *status);
+int crdt_pncounter_ops_egress(crdt_ctx *ctx, const crdt_dot_ops *ops, size_t N, const uint32_t *actors, size_t A,
+                              uint64_t *frame_off, uint8_t *bytes, size_t cap, size_t *total, uint32_t *status);
+int crdt_gset_ops_egress(crdt_ctx *ctx, const crdt_dot_ops *ops, size_t N, const uint64_t *elems, size_t U,
+                         uint64_t *frame_off, uint8_t *bytes, size_t cap, size_t *total, uint32_t *status);
+int crdt_lwwreg_ops_egress(crdt_ctx *ctx, const crdt_lwwreg_ops *ops, size_t N, uint64_t *frame_off, uint8_t *bytes,
+                           size_t cap, size_t *total, uint32_t *status);
 
 /* ---- synthetic inputs (bench / test data, generated in HBM) --------------------------------
  * Counter-based and reproducible on the CPU (oracle/oracle.py synth_* restates them; small

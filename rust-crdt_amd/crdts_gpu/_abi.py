@@ -70,6 +70,9 @@ EXPORTS = (
     "crdt_map_counter_ops_egress", "crdt_map_orswot_ops_egress", "crdt_map_nested_ops_egress",
     "crdt_mvreg_forget_batch", "crdt_mvreg_ingest", "crdt_mvreg_egress", "crdt_mvreg_ops_ingest",
     "crdt_mvreg_ops_egress",
+    "crdt_lwwreg_apply_batch",
+    "crdt_vclock_ops_ingest", "crdt_pncounter_ops_ingest", "crdt_gset_ops_ingest", "crdt_lwwreg_ops_ingest",
+    "crdt_vclock_ops_egress", "crdt_pncounter_ops_egress", "crdt_gset_ops_egress", "crdt_lwwreg_ops_egress",
 )
 
 
@@ -226,6 +229,22 @@ class MVRegOps(ctypes.Structure):  # crdt_mvreg_ops
 
 class MVRegOpsBuf(ctypes.Structure):  # crdt_mvreg_ops_buf: MVRegOps with capacities for counts
     _fields_ = [("op_cap", S), ("op_off", P), ("clk_row", P), ("clk_pool", P), ("row_cap", S), ("val", P)]
+
+
+class LwwRegOps(ctypes.Structure):  # crdt_lwwreg_ops
+    _fields_ = [("n_ops", S), ("op_off", P), ("marker", P), ("val", P)]
+
+
+class LwwRegOpsBuf(ctypes.Structure):  # crdt_lwwreg_ops_buf: LwwRegOps with op_cap for n_ops
+    _fields_ = [("op_cap", S), ("op_off", P), ("marker", P), ("val", P)]
+
+
+class DotOps(ctypes.Structure):  # crdt_dot_ops
+    _fields_ = [("n_ops", S), ("op_off", P), ("state_idx", P), ("actor", P), ("counter", P), ("dir", P)]
+
+
+class DotOpsBuf(ctypes.Structure):  # crdt_dot_ops_buf: DotOps with op_cap for n_ops
+    _fields_ = [("op_cap", S), ("op_off", P), ("state_idx", P), ("actor", P), ("counter", P), ("dir", P)]
 
 
 # crdt_comm_ops: the caller's own collectives (host buffers)
@@ -458,6 +477,14 @@ _SIGS.update({  # MVReg on its own: forget and the wire forms (csrc/mvreg_forget
     "crdt_mvreg_ops_ingest": ([P, P, P, S, P, S, ctypes.POINTER(MVRegOpsBuf), P, ctypes.POINTER(U64)], ctypes.c_int),
     "crdt_mvreg_ops_egress": ([P, ctypes.POINTER(MVRegOps), S, P, S, P, P, S, ctypes.POINTER(S), P], ctypes.c_int),
 })
+_SIGS.update({  # LWWReg apply and the lattice types' op streams (csrc/lwwreg_apply.hip, csrc/wire_lattice_ops.hip)
+    "crdt_lwwreg_apply_batch": ([P, P, P, S, ctypes.POINTER(LwwRegOps), P, P], ctypes.c_int),
+    "crdt_lwwreg_ops_ingest": ([P, P, P, S, ctypes.POINTER(LwwRegOpsBuf), P, ctypes.POINTER(U64)], ctypes.c_int),
+    "crdt_lwwreg_ops_egress": ([P, ctypes.POINTER(LwwRegOps), S, P, P, S, ctypes.POINTER(S), P], ctypes.c_int),
+})
+for _t in ("vclock", "pncounter", "gset"):
+    _SIGS[f"crdt_{_t}_ops_ingest"] = ([P, P, P, S, P, S, ctypes.POINTER(DotOpsBuf), P, ctypes.POINTER(U64)], ctypes.c_int)
+    _SIGS[f"crdt_{_t}_ops_egress"] = ([P, ctypes.POINTER(DotOps), S, P, S, P, P, S, ctypes.POINTER(S), P], ctypes.c_int)
 for _t in ("vclock", "gcounter", "pncounter", "gset"):
     _SIGS[f"crdt_{_t}_lub_many"] = ([P, P, S, S, S, S, S, P, S, ctypes.c_uint], ctypes.c_int)
     _SIGS[f"crdt_{_t}_merge_batch"] = ([P, P, P, S, S, S, S], ctypes.c_int)

@@ -21,6 +21,10 @@ orswot_apply_batch / nested_apply_batch take.
 MVReg<u64, u32> on its own: mvreg_ingest / mvreg_egress move register frames to and from the dense
 (vclk, vval) of mvreg.py, mvreg_ops_ingest / mvreg_ops_egress Vec<mvreg::Op> frames to and from the
 MVRegOpBatch mvreg.apply_batch takes.
+
+The lattice types' ops are fixed-width records: vclock_ops_ingest (VClock and GCounter: Vec<Dot<u32>>),
+pncounter_ops_ingest, gset_ops_ingest and lwwreg_ops_ingest return the arrays apply.apply_dots /
+apply.apply_inserts / lwwreg.apply_batch take; the four *_ops_egress twins write them back as frames.
 """
 from __future__ import annotations
 
@@ -1014,3 +1018,209 @@ def mvreg_ops_egress(ops, actors: torch.Tensor, ctx: Optional[Context] = None):
     ctx.call("crdt_mvreg_ops_egress", *args, dptr(frame_off), dptr(data), data.numel(), ctypes.byref(total),
              dptr(status))
     return frame_off, data[:total.value], status
+
+
+# ---- the lattice types' op streams (include/crdt_gpu.h "the lattice types' op streams") --------------
+class DotOpBatch(NamedTuple):
+    """Ops of VClock / GCounter / PNCounter / GSet grouped by state: state_idx / actor / counter (/ dir)
+    go to apply.apply_dots, state_idx / element to apply.apply_inserts."""
+    op_off: torch.Tensor              # (N+1,) int64
+    state_idx: torch.Tensor           # (n_ops,) int32
+    actor: torch.Tensor               # (n_ops,) int32: the dense actor index (GSet: the element index)
+    counter: Optional[torch.Tensor]   # (n_ops,) int64; None for GSet
+    dir: Optional[torch.Tensor]       # (n_ops,) uint8, PNCounter only
+
+    @property
+    def element(self) -> torch.Tensor:
+        return self.actor
+
+
+class DotOpsIngest(NamedTuple):
+    """Result of vclock_ops_ingest / pncounter_ops_ingest / gset_ops_ingest."""
+    ops: DotOpBatch
+    status: torch.Tensor      # (N,) int32: BAD / MISSING / CAP bits
+    totals: Optional[tuple]   # (ops,) of the well-formed frames; None with sync=False
+
+
+class LwwRegOpsIngest(NamedTuple):
+    """Result of lwwreg_ops_ingest."""
+    ops: tuple                # lwwreg.LwwRegOpBatch: goes to lwwreg.apply_batch unchanged
+    status: torch.Tensor
+    totals: Optional[tuple]
+
+
+def _lops_caps(what, sync, caps):
+    if sync:
+        if caps is not None:
+            raise ValueError(f"{what}: capacities are chosen by the sizing call unless sync=False")
+        return None
+    if caps is None or len(caps) != 1 or int(caps[0]) < 0:
+        raise ValueError(f"{what}: sync=False needs caps=(op_cap,)")
+    return int(caps[0])
+
+
+def _lops_frames(what, data, frame_off, d=None, d_dt=None, d_nm=None):
+    ts = [(data, "bytes", (torch.uint8,)), (frame_off, "frame_off", (torch.int64,))]
+    if d_nm:
+        ts.append((d, d_nm, (d_dt,)))
+    _ops_check(what, ts)
+    if data.dim() != 1 or frame_off.dim() != 1 or frame_off.shape[0] < 1:
+        raise ValueError(f"{what}: bytes must be a uint8 vector and frame_off an int64 (N+1,) tensor")
+    if d_nm and (d.dim() != 1 or d.shape[0] == 0):
+        raise ValueError(f"{what}: the {d_nm} dictionary must be a non-empty vector")
+    return frame_off.shape[0] - 1
+
+
+def _dot_ops_ingest(what, kind, data, frame_off, d, d_dt, d_nm, sync, caps, ctx):
+    cap = _lops_caps(what, sync, caps)
+    N = _lops_frames(what, data, frame_off, d, d_dt, d_nm)
+    fn = f"crdt_{kind}_ops_ingest"
+    ctx = _ctx(data, ctx)
+    dev = data.device
+    status = torch.empty(N, dtype=torch.int32, device=dev)
+    op_off = torch.empty(N + 1, dtype=torch.int64, device=dev)
+    head = (_ptr_or_dummy(data), dptr(frame_off), N, dptr(d), d.shape[0])
+    totals = None
+    if sync:
+        tot = (ctypes.c_uint64 * 1)()
+        if N:
+            ctx.call(fn, *head, None, dptr(status), tot)
+        totals = (int(tot[0]),)
+        cap = totals[0]
+    if sync:
+        state_idx = torch.empty(cap, dtype=torch.int32, device=dev)
+    else:  # entries past the ops kept are never written: an apply of the whole arrays skips them
+        state_idx = torch.full((cap,), -1, dtype=torch.int32, device=dev)
+    col = torch.empty(cap, dtype=torch.int32, device=dev)
+    counter = torch.empty(cap, dtype=torch.int64, device=dev) if kind != "gset" else None
+    dr = torch.empty(cap, dtype=torch.uint8, device=dev) if kind == "pncounter" else None
+    b = _abi.DotOpsBuf(cap, dptr(op_off), _ptr_or_dummy(state_idx), _ptr_or_dummy(col),
+                       None if counter is None else _ptr_or_dummy(counter), None if dr is None else _ptr_or_dummy(dr))
+    if N:
+        ctx.call(fn, *head, ctypes.byref(b), dptr(status), None)
+    else:
+        op_off.zero_()
+    return DotOpsIngest(DotOpBatch(op_off, state_idx, col, counter, dr), status, totals)
+
+
+def vclock_ops_ingest(data: torch.Tensor, frame_off: torch.Tensor, actors: torch.Tensor, sync: bool = True, caps=None,
+                      ctx: Optional[Context] = None) -> DotOpsIngest:
+    """Frames of Vec<Dot<u32>> (one per VClock / GCounter state) -> DotOpsIngest.  sync=True sizes
+    first (one host synchronisation) and allocates exactly; sync=False takes caps=(op_cap,), never
+    synchronises, and marks the states past the capacity with CAP (op_cap = sum((B_s - 8) // 12)
+    over the frames always suffices)."""
+    return _dot_ops_ingest("wire.vclock_ops_ingest", "vclock", data, frame_off, actors, torch.int32, "actors", sync,
+                           caps, ctx)
+
+
+def pncounter_ops_ingest(data: torch.Tensor, frame_off: torch.Tensor, actors: torch.Tensor, sync: bool = True,
+                         caps=None, ctx: Optional[Context] = None) -> DotOpsIngest:
+    """Frames of Vec<pncounter::Op<u32>> -> DotOpsIngest with dir (0 = Pos, 1 = Neg); 16-byte records."""
+    return _dot_ops_ingest("wire.pncounter_ops_ingest", "pncounter", data, frame_off, actors, torch.int32, "actors",
+                           sync, caps, ctx)
+
+
+def gset_ops_ingest(data: torch.Tensor, frame_off: torch.Tensor, elems: torch.Tensor, sync: bool = True, caps=None,
+                    ctx: Optional[Context] = None) -> DotOpsIngest:
+    """Frames of Vec<u64> (GSet ops) -> DotOpsIngest whose ops.element is the dense element index in
+    the sorted u64 dictionary `elems`; 8-byte records."""
+    return _dot_ops_ingest("wire.gset_ops_ingest", "gset", data, frame_off, elems, torch.int64, "elems", sync, caps,
+                           ctx)
+
+
+def lwwreg_ops_ingest(data: torch.Tensor, frame_off: torch.Tensor, sync: bool = True, caps=None,
+                      ctx: Optional[Context] = None) -> LwwRegOpsIngest:
+    """Frames of Vec<LWWReg<u64, u64>> (one per register) -> LwwRegOpsIngest with a
+    lwwreg.LwwRegOpBatch; 16-byte records (val, marker), no dictionary."""
+    from .lwwreg import LwwRegOpBatch
+    what = "wire.lwwreg_ops_ingest"
+    cap = _lops_caps(what, sync, caps)
+    N = _lops_frames(what, data, frame_off)
+    ctx = _ctx(data, ctx)
+    dev = data.device
+    status = torch.empty(N, dtype=torch.int32, device=dev)
+    op_off = torch.empty(N + 1, dtype=torch.int64, device=dev)
+    head = (_ptr_or_dummy(data), dptr(frame_off), N)
+    totals = None
+    if sync:
+        tot = (ctypes.c_uint64 * 1)()
+        if N:
+            ctx.call("crdt_lwwreg_ops_ingest", *head, None, dptr(status), tot)
+        totals = (int(tot[0]),)
+        cap = totals[0]
+    marker = torch.empty(cap, dtype=torch.int64, device=dev)
+    val = torch.empty(cap, dtype=torch.int64, device=dev)
+    b = _abi.LwwRegOpsBuf(cap, dptr(op_off), _ptr_or_dummy(marker), _ptr_or_dummy(val))
+    if N:
+        ctx.call("crdt_lwwreg_ops_ingest", *head, ctypes.byref(b), dptr(status), None)
+    else:
+        op_off.zero_()
+    return LwwRegOpsIngest(LwwRegOpBatch(op_off, marker, val), status, totals)
+
+
+def _lops_egress(ctx, fn, N, dev, *args):
+    status = torch.empty(N, dtype=torch.int32, device=dev)
+    frame_off = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+    total = ctypes.c_size_t()
+    ctx.call(fn, *args, dptr(frame_off), None, 0, ctypes.byref(total), dptr(status))
+    data = torch.empty(max(total.value, 1), dtype=torch.uint8, device=dev)
+    ctx.call(fn, *args, dptr(frame_off), dptr(data), data.numel(), ctypes.byref(total), dptr(status))
+    return frame_off, data[:total.value], status
+
+
+def _dot_ops_egress(what, kind, ops, d, d_dt, d_nm, ctx):
+    for nm in ("op_off", "actor", "counter", "dir"):
+        if not hasattr(ops, nm):
+            raise ValueError(f"{what}: expected an op batch with fields {DotOpBatch._fields}")
+    ts = [(ops.op_off, "op_off", _I64), (ops.actor, "actor", _I32), (d, d_nm, (d_dt,))]
+    if kind != "gset":
+        ts.append((ops.counter, "counter", _I64))
+    if kind == "pncounter":
+        ts.append((ops.dir, "dir", (torch.uint8,)))
+    _ops_check(what, ts)
+    n = ops.actor.shape[0]
+    if d.dim() != 1 or d.shape[0] == 0:
+        raise ValueError(f"{what}: the {d_nm} dictionary must be a non-empty vector")
+    if ops.op_off.dim() != 1 or ops.op_off.shape[0] < 1 or any(tuple(t.shape) != (n,) for t, _, _ in ts[3:]) \
+            or ops.actor.dim() != 1:
+        raise ValueError(f"{what}: op_off (N+1,) and (n_ops,) op arrays expected")
+    N = ops.op_off.shape[0] - 1
+    o = _abi.DotOps(n, dptr(ops.op_off), None, _ptr_or_dummy(ops.actor),
+                    None if kind == "gset" else _ptr_or_dummy(ops.counter),
+                    _ptr_or_dummy(ops.dir) if kind == "pncounter" else None)
+    ctx = _ctx(ops.op_off, ctx)
+    return _lops_egress(ctx, f"crdt_{kind}_ops_egress", N, ops.op_off.device, ctypes.byref(o), N, dptr(d), d.shape[0])
+
+
+def vclock_ops_egress(ops, actors: torch.Tensor, ctx: Optional[Context] = None):
+    """DotOpBatch -> (frame_off (N+1,), bytes, status (N,) int32): one Vec<Dot<u32>> frame per state.
+    status bit 1 (MISSING): the state had an op with no wire form (an actor index >= A, an invalid
+    op_off) and its frame is the empty Vec.  state_idx is not read."""
+    return _dot_ops_egress("wire.vclock_ops_egress", "vclock", ops, actors, torch.int32, "actors", ctx)
+
+
+def pncounter_ops_egress(ops, actors: torch.Tensor, ctx: Optional[Context] = None):
+    """As vclock_ops_egress for Vec<pncounter::Op<u32>> frames (a dir > 1 has no wire form)."""
+    return _dot_ops_egress("wire.pncounter_ops_egress", "pncounter", ops, actors, torch.int32, "actors", ctx)
+
+
+def gset_ops_egress(ops, elems: torch.Tensor, ctx: Optional[Context] = None):
+    """As vclock_ops_egress for Vec<u64> frames: ops.actor holds the element indices into `elems`."""
+    return _dot_ops_egress("wire.gset_ops_egress", "gset", ops, elems, torch.int64, "elems", ctx)
+
+
+def lwwreg_ops_egress(ops, ctx: Optional[Context] = None):
+    """lwwreg.LwwRegOpBatch -> (frame_off (N+1,), bytes, status (N,) int32): one Vec<LWWReg> frame per
+    register; status bit 1: an invalid op_off (the empty Vec)."""
+    from .lwwreg import LwwRegOpBatch
+    what = "wire.lwwreg_ops_egress"
+    if not hasattr(ops, "_fields") or tuple(ops._fields) != LwwRegOpBatch._fields:
+        raise ValueError(f"{what}: expected an op batch with fields {LwwRegOpBatch._fields}")
+    _ops_check(what, ((ops.op_off, "op_off", _I64), (ops.marker, "marker", _I64), (ops.val, "val", _I64)))
+    n = ops.marker.shape[0]
+    if ops.op_off.dim() != 1 or ops.op_off.shape[0] < 1 or ops.marker.dim() != 1 or tuple(ops.val.shape) != (n,):
+        raise ValueError(f"{what}: op_off (N+1,) and marker / val (n_ops,) expected")
+    N = ops.op_off.shape[0] - 1
+    o = _abi.LwwRegOps(n, dptr(ops.op_off), _ptr_or_dummy(ops.marker), _ptr_or_dummy(ops.val))
+    ctx = _ctx(ops.op_off, ctx)
+    return _lops_egress(ctx, "crdt_lwwreg_ops_egress", N, ops.op_off.device, ctypes.byref(o), N)
