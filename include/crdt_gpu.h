@@ -1091,6 +1091,45 @@ int crdt_mvreg_apply_batch(crdt_ctx *ctx, const crdt_mvreg_states *states, const
 int crdt_mvreg_forget_batch(crdt_ctx *ctx, const crdt_mvreg_states *states, const uint64_t *y, size_t y_stride,
                             uint32_t *status);
 
+/* ---- batched state equality: the reference's PartialEq on N pairs of states ------------------
+ * ne[i] (device u32[N], written for every i) is 0 iff x[i] == y[i] by the reference's PartialEq:
+ * derived on Orswot (orswot.rs:20), Map / Entry (map.rs:31-47) and VClock (vclock.rs:56),
+ * hand-written and order-free on MVReg (mvreg.rs:62-86).  Otherwise it is the COMPLETE set of the
+ * components that differ (there is no early exit between components).  Both sides are read only; x
+ * and y may be the same memory (every word is then 0).  The layouts are those of the matching
+ * merge_batch: crdt_mvreg_states, crdt_orswot_states, crdt_map_states + crdt_map_deferred.
+ *  - Clock rows and entry rows (Orswot member rows, Map entry clocks) compare word by word over the
+ *    full u64.  An absent member / key is an all-zero row, so this is the BTreeMap / HashMap equality
+ *    of the derived impls (vclock.rs:56, orswot.rs:20, map.rs:31-47).
+ *  - Registers (an MVReg, and every key of a Map) compare as SETS of (clock row, value) over the
+ *    non-empty slots, the two loops of mvreg.rs:64-81: an empty slot (all-zero clock) is skipped
+ *    wherever it sits, V may differ between the sides, slot order is irrelevant, and the value IS
+ *    compared (the same clock with another value is unequal, unlike merge, which never looks at
+ *    values).  A pair held twice within one side counts once: the sanity assert_eq!(num_found, 1) of
+ *    mvreg.rs:71 / :80 is not reproduced as a failure.  A Map key that is absent (all-zero entry
+ *    clock) has the empty register whatever its value slots hold (map.rs:40-47: no Entry, no val).
+ *  - Deferred removes: the first def_count[s] slots of each side are a map rm clock -> member / key
+ *    set (orswot.rs:24, map.rs:37).  Slot order and Dcap are irrelevant; slots of one side holding the
+ *    same clock union their sets, as merge_batch treats them; a slot with an empty set is still a key
+ *    of the map ({c: {}} != {}, as in the reference's HashMap).  Bits past M / K in a bitmap's last
+ *    word are zero by the layout's invariant and are not masked.
+ * Limits (those of the matching merge_batch; past them CRDT_EUNSUPPORTED before any launch):
+ * A <= 1024; MVReg 1 <= V <= 16; Map 1 <= V <= 32 on each side.  N, and M / K / A where applicable,
+ * must match across the sides (CRDT_EINVAL).  Dcap and def_count are not bounded: the result is exact
+ * for any number of live slots.  N == 0 returns CRDT_OK.  Device memory only.  A deferred side with
+ * Dcap == 0 may pass NULL buffers (crdt_map_eq_batch: a NULL crdt_map_deferred); a def_count that IS
+ * passed is read whatever Dcap is, so a non-zero count with Dcap == 0 reports CRDT_NE_INVALID. */
+#define CRDT_NE_CLOCK    1u  /* the state's own clock differs                                  */
+#define CRDT_NE_ENTRIES  2u  /* Orswot: some member's dot row; Map: some key's entry clock     */
+#define CRDT_NE_VALUES   4u  /* MVReg / Map: some register differs as a set of (clock, value)  */
+#define CRDT_NE_DEFERRED 8u  /* the deferred removes differ as a map rm clock -> set           */
+#define CRDT_NE_INVALID 16u  /* def_count above Dcap on either side: no other bit is set       */
+
+int crdt_mvreg_eq_batch(crdt_ctx *ctx, const crdt_mvreg_states *x, const crdt_mvreg_states *y, uint32_t *ne);
+int crdt_orswot_eq_batch(crdt_ctx *ctx, const crdt_orswot_states *x, const crdt_orswot_states *y, uint32_t *ne);
+int crdt_map_eq_batch(crdt_ctx *ctx, const crdt_map_states *x, const crdt_map_deferred *xd, const crdt_map_states *y,
+                      const crdt_map_deferred *yd, uint32_t *ne);
+
 /* ---- causal helpers on dense clock rows -----------------------------------
  * Row-pair ops over N pairs (x_i, y_i) of A-word rows (VClock, GCounter inner, or a PNCounter
  * P‖N row with A = 2·actors):

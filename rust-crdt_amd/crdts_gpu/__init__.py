@@ -7,6 +7,8 @@ structure-of-arrays states in HBM, through libcrdt_gpu.so (include/crdt_gpu.h).
 There is no CPU fallback: without the HIP library every call raises CrdtGpuUnavailable.
 """
 from ._abi import CrdtGpuError, CrdtGpuUnavailable, load as load_library  # noqa: F401
+from ._abi import (CRDT_NE_CLOCK as NE_CLOCK, CRDT_NE_ENTRIES as NE_ENTRIES, CRDT_NE_VALUES as NE_VALUES,  # noqa: F401
+                   CRDT_NE_DEFERRED as NE_DEFERRED, CRDT_NE_INVALID as NE_INVALID)
 from .context import Context, synth_fill  # noqa: F401
 from ._lattice import lub_many_multi  # noqa: F401
 from .readctx import AddCtx, ReadCtx, RmCtx, derive_add_ctx, derive_rm_ctx  # noqa: F401

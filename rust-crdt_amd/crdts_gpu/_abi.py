@@ -24,6 +24,8 @@ CRDT_ABI_VERSION = 8  # include/crdt_gpu.h
 CRDT_MEM_HOST = 1
 CRDT_KIND = {"vclock": 1, "gcounter": 2, "pncounter": 3, "gset": 4}
 CRDT_RED_MAX, CRDT_RED_MIN, CRDT_RED_SUM = 0, 1, 2
+# crdt_*_eq_batch: the components that differ
+CRDT_NE_CLOCK, CRDT_NE_ENTRIES, CRDT_NE_VALUES, CRDT_NE_DEFERRED, CRDT_NE_INVALID = 1, 2, 4, 8, 16
 
 # Every symbol declared in include/crdt_gpu.h (checked by tests/test_abi.py).
 EXPORTS = (
@@ -73,6 +75,7 @@ EXPORTS = (
     "crdt_lwwreg_apply_batch",
     "crdt_vclock_ops_ingest", "crdt_pncounter_ops_ingest", "crdt_gset_ops_ingest", "crdt_lwwreg_ops_ingest",
     "crdt_vclock_ops_egress", "crdt_pncounter_ops_egress", "crdt_gset_ops_egress", "crdt_lwwreg_ops_egress",
+    "crdt_mvreg_eq_batch", "crdt_orswot_eq_batch", "crdt_map_eq_batch",
 )
 
 
@@ -481,6 +484,12 @@ _SIGS.update({  # LWWReg apply and the lattice types' op streams (csrc/lwwreg_ap
     "crdt_lwwreg_apply_batch": ([P, P, P, S, ctypes.POINTER(LwwRegOps), P, P], ctypes.c_int),
     "crdt_lwwreg_ops_ingest": ([P, P, P, S, ctypes.POINTER(LwwRegOpsBuf), P, ctypes.POINTER(U64)], ctypes.c_int),
     "crdt_lwwreg_ops_egress": ([P, ctypes.POINTER(LwwRegOps), S, P, P, S, ctypes.POINTER(S), P], ctypes.c_int),
+})
+_SIGS.update({  # batched state equality (csrc/eq.hip)
+    "crdt_mvreg_eq_batch": ([P, ctypes.POINTER(MVRegStates), ctypes.POINTER(MVRegStates), P], ctypes.c_int),
+    "crdt_orswot_eq_batch": ([P, ctypes.POINTER(OrswotStates), ctypes.POINTER(OrswotStates), P], ctypes.c_int),
+    "crdt_map_eq_batch": ([P, ctypes.POINTER(MapStates), ctypes.POINTER(MapDeferred), ctypes.POINTER(MapStates),
+                           ctypes.POINTER(MapDeferred), P], ctypes.c_int),
 })
 for _t in ("vclock", "pncounter", "gset"):
     _SIGS[f"crdt_{_t}_ops_ingest"] = ([P, P, P, S, P, S, ctypes.POINTER(DotOpsBuf), P, ctypes.POINTER(U64)], ctypes.c_int)

@@ -422,6 +422,21 @@ def merge_batch(self_states: MapStates, other: MapStates, ctx: Optional[Context]
     return status
 
 
+def eq_batch(x: MapStates, y: MapStates, ctx: Optional[Context] = None) -> torch.Tensor:
+    """x[i] == y[i] by Map's derived PartialEq (map.rs:31-47) with MVReg's order-free one per key
+    (mvreg.rs:62-86); V and Dcap may differ between the sides.  Returns ne (N,) int32: 0 = equal, else
+    the OR of NE_CLOCK / NE_ENTRIES / NE_VALUES / NE_DEFERRED for every component that differs, or
+    NE_INVALID alone when a def_count is above its Dcap.  Both sides are read only."""
+    ctx = ctx or Context.default(x.clock.device.index)
+    a, ad = _map_states_structs(ctx, x, "map.eq_batch(x)")
+    b, bd = _map_states_structs(ctx, y, "map.eq_batch(y)")
+    if (a.N, a.K, a.A) != (b.N, b.K, b.A):
+        raise ValueError("map.eq_batch: x and y differ in N, K or A")
+    ne = torch.empty(a.N, dtype=torch.int32, device=x.clock.device)
+    ctx.call("crdt_map_eq_batch", ctypes.byref(a), ctypes.byref(ad), ctypes.byref(b), ctypes.byref(bd), ne.data_ptr())
+    return ne
+
+
 # ---- Map<K, GCounter> / Map<K, PNCounter> (crdt_map_counter_lub_many, round 4) ----------------------
 class MapCounterLub(NamedTuple):
     clock: torch.Tensor               # (G, A)

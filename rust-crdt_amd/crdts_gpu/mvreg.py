@@ -9,6 +9,7 @@ Dense register (the value layout of the Map entry points): slots in Vec order,
     apply_batch(vclk (N, V, A), vval, ops)           reg[i].apply(op) for its ops in order   (mvreg.rs:130-166)
     read(vclk (N, V, A), vval)                       reg[i].read() as a ReadCtx              (mvreg.rs:183-215)
     forget_batch(vclk (N, V, A), vval, y)            reg[i].forget(y or y[i]), in place      (mvreg.rs:88-104)
+    eq_batch(x (N, Vx, A), x_vval, y (N, Vy, A), y_vval)  x[i] == y[i], order-free            (mvreg.rs:62-86)
 The wire forms (register frames, Vec<Op::Put> frames) are in wire.py: mvreg_ingest / mvreg_egress /
 mvreg_ops_ingest / mvreg_ops_egress.
 """
@@ -100,6 +101,21 @@ def merge_batch(self_vclk: torch.Tensor, self_vval: torch.Tensor, other_vclk: to
     status = torch.empty(a.N, dtype=torch.int32, device=self_vclk.device)
     ctx.call("crdt_mvreg_merge_batch", ctypes.byref(a), ctypes.byref(b), status.data_ptr())
     return status
+
+
+def eq_batch(x_vclk: torch.Tensor, x_vval: torch.Tensor, y_vclk: torch.Tensor, y_vval: torch.Tensor,
+             ctx: Optional[Context] = None) -> torch.Tensor:
+    """x[i] == y[i] by MVReg's PartialEq (mvreg.rs:62-86) on (N, V, A) / (N, V) registers: sets of
+    (clock, value) over the non-empty slots, so slot order, holes and V (which may differ between the
+    sides) do not matter.  Returns ne (N,) int32: 0 = equal, else NE_VALUES.  Both sides are read only."""
+    ctx = ctx or Context.default(x_vclk.device.index)
+    a = _states(ctx, x_vclk, x_vval, "mvreg.eq_batch(x)")
+    b = _states(ctx, y_vclk, y_vval, "mvreg.eq_batch(y)")
+    if (a.N, a.A) != (b.N, b.A):
+        raise ValueError("mvreg.eq_batch: x and y differ in N or A")
+    ne = torch.empty(a.N, dtype=torch.int32, device=x_vclk.device)
+    ctx.call("crdt_mvreg_eq_batch", ctypes.byref(a), ctypes.byref(b), ne.data_ptr())
+    return ne
 
 
 class MVRegOpBatch(NamedTuple):

@@ -400,6 +400,21 @@ def merge_batch(self_states: OrswotStates, other: OrswotStates, ctx: Optional[Co
     return status
 
 
+def eq_batch(x: OrswotStates, y: OrswotStates, ctx: Optional[Context] = None) -> torch.Tensor:
+    """x[i] == y[i] by Orswot's derived PartialEq (orswot.rs:20): clock, member rows and the deferred
+    removes as a map rm clock -> member set (slot order and Dcap do not matter).  Returns ne (N,)
+    int32: 0 = equal, else the OR of NE_CLOCK / NE_ENTRIES / NE_DEFERRED for every component that
+    differs, or NE_INVALID alone when a def_count is above its Dcap.  Both sides are read only."""
+    ctx = ctx or Context.default(x.clock.device.index)
+    a = _states_struct(ctx, x, "orswot.eq_batch(x)")
+    b = _states_struct(ctx, y, "orswot.eq_batch(y)")
+    if (a.N, a.M, a.A) != (b.N, b.M, b.A):
+        raise ValueError("orswot.eq_batch: x and y differ in N, M or A")
+    ne = torch.empty(a.N, dtype=torch.int32, device=x.clock.device)
+    ctx.call("crdt_orswot_eq_batch", ctypes.byref(a), ctypes.byref(b), dptr(ne))
+    return ne
+
+
 # ---------------------------------------------------------------------------------------------
 # Batched reads: Orswot::read / contains (orswot.rs:253-279) as ReadCtx (readctx.py)
 # ---------------------------------------------------------------------------------------------
