@@ -148,13 +148,18 @@ def orswot_ingest(data: torch.Tensor, frame_off: torch.Tensor, actors: torch.Ten
     return OrswotFrames(clock, entries, def_off, dcl[:min(D, cap)], dmb[:min(D, cap)], st)
 
 
-def _egress(ctx, fn, N, dev, *args):
-    frame_off = torch.empty(N + 1, dtype=torch.int64, device=dev)
+def _egress(ctx, fn, N, dev, *args, with_status=False):
+    """The two calls of every egress: the sizing call, the allocation, the write call ->
+    (frame_off, bytes), and with_status (the op streams) the (N,) int32 status the calls fill.
+    frame_off starts zeroed: the C calls return at N == 0 without writing it."""
+    frame_off = torch.zeros(N + 1, dtype=torch.int64, device=dev)
     total = ctypes.c_size_t()
-    ctx.call(fn, *args, dptr(frame_off), None, 0, ctypes.byref(total))
+    status = torch.empty(N, dtype=torch.int32, device=dev) if with_status else None
+    tail = (ctypes.byref(total),) + ((dptr(status),) if with_status else ())
+    ctx.call(fn, *args, dptr(frame_off), None, 0, *tail)
     data = torch.empty(max(total.value, 1), dtype=torch.uint8, device=dev)
-    ctx.call(fn, *args, dptr(frame_off), dptr(data), data.numel(), ctypes.byref(total))
-    return frame_off, data[:total.value]
+    ctx.call(fn, *args, dptr(frame_off), dptr(data), data.numel(), *tail)
+    return (frame_off, data[:total.value]) + ((status,) if with_status else ())
 
 
 def vclock_egress(rows: torch.Tensor, actors: torch.Tensor, ctx: Optional[Context] = None, _fn="crdt_vclock_egress",
@@ -500,67 +505,84 @@ def _ops_check(what: str, tensors) -> None:
             raise ValueError(f"{what}({nm}): tensor on {t.device}; the others are on {dev}")
 
 
-def _ops_frames(what, data, frame_off, actors, ids, id_dt, id_nm):
-    _ops_check(what, ((data, "bytes", (torch.uint8,)), (frame_off, "frame_off", (torch.int64,)),
-                      (actors, "actors", (torch.int32,)), (ids, id_nm, (id_dt,))))
+def _frames_check(what, data, frame_off, dicts):
+    """The frames and the dictionaries [(tensor, name, dtype)] of an op-stream ingest -> N."""
+    _ops_check(what, [(data, "bytes", (torch.uint8,)), (frame_off, "frame_off", (torch.int64,))]
+               + [(d, nm, (dt,)) for d, nm, dt in dicts])
     if data.dim() != 1 or frame_off.dim() != 1 or frame_off.shape[0] < 1:
         raise ValueError(f"{what}: bytes must be a uint8 vector and frame_off an int64 (N+1,) tensor")
-    if actors.dim() != 1 or ids.dim() != 1 or actors.shape[0] == 0 or ids.shape[0] == 0:
+    if any(d.dim() != 1 or d.shape[0] == 0 for d, _, _ in dicts):
         raise ValueError(f"{what}: the dictionaries must be non-empty vectors")
-    return frame_off.shape[0] - 1, actors.shape[0], ids.shape[0]
+    return frame_off.shape[0] - 1
 
 
-def _ops_caps(what, sync, caps):
+def _d32(d, nm):
+    return d, nm, torch.int32
+
+
+def _caps_check(what, sync, caps, names):
+    """sync=True takes no capacities (the sizing call chooses them), sync=False one per name."""
     if sync:
         if caps is not None:
             raise ValueError(f"{what}: capacities are chosen by the sizing call unless sync=False")
         return None
-    if caps is None or len(caps) != 3 or any(int(c) < 0 for c in caps):
-        raise ValueError(f"{what}: sync=False needs caps=(op_cap, row_cap, id_cap)")
+    if caps is None or len(caps) != len(names) or any(int(c) < 0 for c in caps):
+        raise ValueError(f"{what}: sync=False needs caps=({', '.join(names)}{',' if len(names) == 1 else ''})")
     return tuple(int(c) for c in caps)
 
 
-def _ops_ingest(what, fn, buf_cls, is_map, data, frame_off, actors, ids, N, A, sync, caps, ctx):
-    from .map import MapOpBatch
-    from .orswot import OrswotOpBatch
+def _sized_ingest(fn, data, frame_off, N, dict_args, n_firsts, n_totals, sync, caps, alloc, ctx):
+    """The skeleton of every sized op-stream ingest: the sizing call (sync; its n_totals sums become the
+    capacities) or the caller's capacities, then the fill.  alloc(caps, op_off) allocates the batch for
+    those capacities -> (the _abi buffer struct, the batch, the batch's list-offset tensors, whose first
+    entry is 0).  -> (batch, status, the n_firsts (N+1,) per-state offset tensors after op_off, totals)."""
     ctx = _ctx(data, ctx)
     dev = data.device
-    U = ids.shape[0]
     status = torch.empty(N, dtype=torch.int32, device=dev)
-    row_off = torch.empty(N + 1, dtype=torch.int64, device=dev)
-    id_off = torch.empty(N + 1, dtype=torch.int64, device=dev)
-    op_off = torch.empty(N + 1, dtype=torch.int64, device=dev)
-    head = (_ptr_or_dummy(data), dptr(frame_off), N, dptr(actors), A, dptr(ids), U)
+    op_off, *firsts = (torch.empty(N + 1, dtype=torch.int64, device=dev) for _ in range(1 + n_firsts))
+    head = (_ptr_or_dummy(data), dptr(frame_off), N, *dict_args)
     totals = None
-    if sync:  # size, then fill with exactly enough room (+ one pad row / id, as encode_ops leaves)
-        tot = (ctypes.c_uint64 * 3)()
+    if sync:
+        tot = (ctypes.c_uint64 * n_totals)()
         if N:
-            ctx.call(fn, *head, None, None, None, dptr(status), tot)
-        totals = (int(tot[0]), int(tot[1]), int(tot[2]))
-        caps = totals
-    n_op, n_row, n_id = caps
-    e = lambda n, dt: torch.empty(n, dtype=dt, device=dev)  # noqa: E731
-    kind, actor, counter, row = e(n_op, torch.uint8), e(n_op, torch.int32), e(n_op, torch.int64), e(n_op, torch.int32)
-    pool = torch.empty((n_row + 1, A), dtype=torch.int64, device=dev)
-    ids_off, idv = e(n_op + 1, torch.int64), e(n_id + 1, torch.int32)
-    pool[n_row].zero_()
-    idv[n_id].zero_()
-    b = buf_cls()
-    b.op_cap, b.row_cap, b.id_cap = n_op, n_row, n_id
-    b.op_off, b.kind, b.actor, b.counter = dptr(op_off), dptr(kind), dptr(actor), dptr(counter)
-    if is_map:
-        key, val = e(n_op, torch.int32), e(n_op, torch.int64)
-        b.key, b.val, b.clk_row, b.clk_pool, b.key_off, b.keys = (dptr(key), dptr(val), dptr(row), dptr(pool),
-                                                                  dptr(ids_off), dptr(idv))
-        ops = MapOpBatch(op_off, kind, actor, counter, key, val, row, pool, ids_off, idv)
-    else:
-        b.rm_row, b.rm_clock, b.mem_off, b.mem = dptr(row), dptr(pool), dptr(ids_off), dptr(idv)
-        ops = OrswotOpBatch(op_off, kind, actor, counter, row, pool, ids_off, idv)
+            ctx.call(fn, *head, None, *((None,) * n_firsts), dptr(status), tot)
+        caps = totals = tuple(int(x) for x in tot)
+    buf, batch, list_offs = alloc(caps, op_off)
     if N:
-        ctx.call(fn, *head, ctypes.byref(b), dptr(row_off), dptr(id_off), dptr(status), None)
+        ctx.call(fn, *head, ctypes.byref(buf), *(dptr(t) for t in firsts), dptr(status), None)
     else:
-        for t in (op_off, row_off, id_off, ids_off[:1]):
+        for t in (op_off, *firsts, *(lo[:1] for lo in list_offs)):
             t.zero_()
+    return batch, status, firsts, totals
+
+
+def _ops_ingest(fn, buf_cls, is_map, data, frame_off, actors, ids, N, sync, caps, ctx):
+    from .map import MapOpBatch
+    from .orswot import OrswotOpBatch
+    dev = data.device
+    A, U = actors.shape[0], ids.shape[0]
+
+    def alloc(caps, op_off):  # exactly enough room + one pad row / id, as encode_ops leaves
+        n_op, n_row, n_id = caps
+        e = lambda n, dt: torch.empty(n, dtype=dt, device=dev)  # noqa: E731
+        kind, actor, counter, row = e(n_op, torch.uint8), e(n_op, torch.int32), e(n_op, torch.int64), e(n_op, torch.int32)
+        pool = torch.empty((n_row + 1, A), dtype=torch.int64, device=dev)
+        ids_off, idv = e(n_op + 1, torch.int64), e(n_id + 1, torch.int32)
+        pool[n_row].zero_()
+        idv[n_id].zero_()
+        b = buf_cls()
+        b.op_cap, b.row_cap, b.id_cap = n_op, n_row, n_id
+        b.op_off, b.kind, b.actor, b.counter = dptr(op_off), dptr(kind), dptr(actor), dptr(counter)
+        if is_map:
+            key, val = e(n_op, torch.int32), e(n_op, torch.int64)
+            b.key, b.val, b.clk_row, b.clk_pool, b.key_off, b.keys = (dptr(key), dptr(val), dptr(row), dptr(pool),
+                                                                      dptr(ids_off), dptr(idv))
+            return b, MapOpBatch(op_off, kind, actor, counter, key, val, row, pool, ids_off, idv), (ids_off,)
+        b.rm_row, b.rm_clock, b.mem_off, b.mem = dptr(row), dptr(pool), dptr(ids_off), dptr(idv)
+        return b, OrswotOpBatch(op_off, kind, actor, counter, row, pool, ids_off, idv), (ids_off,)
+
+    ops, status, (row_off, id_off), totals = _sized_ingest(fn, data, frame_off, N, (dptr(actors), A, dptr(ids), U), 2, 3,
+                                                           sync, caps, alloc, ctx)
     return OpsIngest(ops, status, row_off, id_off, totals)
 
 
@@ -570,10 +592,10 @@ def orswot_ops_ingest(data: torch.Tensor, frame_off: torch.Tensor, actors: torch
     sync=True sizes first (one host synchronisation) and allocates exactly; sync=False takes
     caps=(op_cap, row_cap, id_cap), never synchronises, and marks states past a capacity with CAP."""
     what = "wire.orswot_ops_ingest"
-    caps = _ops_caps(what, sync, caps)
-    N, A, _ = _ops_frames(what, data, frame_off, actors, members, torch.int64, "members")
-    return _ops_ingest(what, "crdt_orswot_ops_ingest", _abi.OrswotOpsBuf, False, data, frame_off, actors,
-                       members, N, A, sync, caps, ctx)
+    caps = _caps_check(what, sync, caps, ("op_cap", "row_cap", "id_cap"))
+    N = _frames_check(what, data, frame_off, [_d32(actors, "actors"), (members, "members", torch.int64)])
+    return _ops_ingest("crdt_orswot_ops_ingest", _abi.OrswotOpsBuf, False, data, frame_off, actors, members, N, sync, caps,
+                       ctx)
 
 
 def map_ops_ingest(data: torch.Tensor, frame_off: torch.Tensor, actors: torch.Tensor, keys: torch.Tensor,
@@ -581,23 +603,14 @@ def map_ops_ingest(data: torch.Tensor, frame_off: torch.Tensor, actors: torch.Te
     """Frames of Vec<map::Op<u32, MVReg<u64, u32>, u32>> -> OpsIngest with a map.MapOpBatch (see
     orswot_ops_ingest for sync / caps; id_cap counts keyset keys)."""
     what = "wire.map_ops_ingest"
-    caps = _ops_caps(what, sync, caps)
-    N, A, _ = _ops_frames(what, data, frame_off, actors, keys, torch.int32, "keys")
-    return _ops_ingest(what, "crdt_map_ops_ingest", _abi.MapOpsBuf, True, data, frame_off, actors, keys, N, A,
-                       sync, caps, ctx)
+    caps = _caps_check(what, sync, caps, ("op_cap", "row_cap", "id_cap"))
+    N = _frames_check(what, data, frame_off, [_d32(actors, "actors"), _d32(keys, "keys")])
+    return _ops_ingest("crdt_map_ops_ingest", _abi.MapOpsBuf, True, data, frame_off, actors, keys, N, sync, caps, ctx)
 
 
-def _ops_egress(what, fn, o, ops, N, actors, ids, ctx):
-    ctx = _ctx(ops.op_off, ctx)
-    dev = ops.op_off.device
-    status = torch.empty(N, dtype=torch.int32, device=dev)
-    args = (ctypes.byref(o), N, dptr(actors), actors.shape[0], dptr(ids), ids.shape[0])
-    frame_off = torch.zeros(N + 1, dtype=torch.int64, device=dev)
-    total = ctypes.c_size_t()
-    ctx.call(fn, *args, dptr(frame_off), None, 0, ctypes.byref(total), dptr(status))
-    data = torch.empty(max(total.value, 1), dtype=torch.uint8, device=dev)
-    ctx.call(fn, *args, dptr(frame_off), dptr(data), data.numel(), ctypes.byref(total), dptr(status))
-    return frame_off, data[:total.value], status
+def _ops_egress(fn, o, ops, N, actors, ids, ctx):
+    return _egress(_ctx(ops.op_off, ctx), fn, N, ops.op_off.device, ctypes.byref(o), N, dptr(actors), actors.shape[0],
+                   dptr(ids), ids.shape[0], with_status=True)
 
 
 def _ops_batch_check(what, ops, fields, actors, ids, id_dt, id_nm, pool_nm):
@@ -634,7 +647,7 @@ def orswot_ops_egress(ops, actors: torch.Tensor, members: torch.Tensor, ctx: Opt
     o.op_off, o.kind, o.actor, o.counter = dptr(ops.op_off), dptr(ops.kind), dptr(ops.actor), dptr(ops.counter)
     o.rm_row, o.rm_clock, o.n_rm_rows = dptr(ops.rm_row), dptr(ops.rm_clock), ops.rm_clock.shape[0]
     o.mem_off, o.mem, o.n_mem = dptr(ops.mem_off), dptr(ops.mem), ops.mem.shape[0]
-    return _ops_egress(what, "crdt_orswot_ops_egress", o, ops, N, actors, members, ctx)
+    return _ops_egress("crdt_orswot_ops_egress", o, ops, N, actors, members, ctx)
 
 
 def map_ops_egress(ops, actors: torch.Tensor, keys: torch.Tensor, ctx: Optional[Context] = None):
@@ -648,7 +661,7 @@ def map_ops_egress(ops, actors: torch.Tensor, keys: torch.Tensor, ctx: Optional[
     o.op_off, o.kind, o.actor, o.counter = dptr(ops.op_off), dptr(ops.kind), dptr(ops.actor), dptr(ops.counter)
     o.key, o.val, o.clk_row, o.clk_pool = dptr(ops.key), dptr(ops.val), dptr(ops.clk_row), dptr(ops.clk_pool)
     o.n_clk_rows, o.key_off, o.keys, o.n_keys = ops.clk_pool.shape[0], dptr(ops.key_off), dptr(ops.keys), ops.keys.shape[0]
-    return _ops_egress(what, "crdt_map_ops_egress", o, ops, N, actors, keys, ctx)
+    return _ops_egress("crdt_map_ops_egress", o, ops, N, actors, keys, ctx)
 
 
 # ---- the value-typed Maps' op streams (include/crdt_gpu.h "value-typed Maps' op streams") -----------
@@ -667,80 +680,48 @@ _VOPS_DTYPES = {"kind": _U8, "vdir": _U8, "vkind": _U8, "ikind": _U8, "actor": _
                 "iactor": _I32, "ikey": _I32, "clk_row": _I32, "keys": _I32, "mems": _I32}  # the rest: 64-bit
 
 
-def _vops_caps(what, sync, caps, n):
-    if sync:
-        if caps is not None:
-            raise ValueError(f"{what}: capacities are chosen by the sizing call unless sync=False")
-        return None
-    if caps is None or len(caps) != n or any(int(c) < 0 for c in caps):
-        names = "(op_cap, row_cap, key_cap, mem_cap)" if n == 4 else "(op_cap, row_cap, key_cap)"
-        raise ValueError(f"{what}: sync=False needs caps={names}")
-    return tuple(int(c) for c in caps)
+_VOPS_CAPS = ("op_cap", "row_cap", "key_cap", "mem_cap")
 
 
-def _vops_frames(what, data, frame_off, actors, keys, third=None, third_dt=None, third_nm=None):
-    dicts = [(actors, "actors", (torch.int32,)), (keys, "keys", (torch.int32,))]
-    if third_nm:
-        dicts.append((third, third_nm, (third_dt,)))
-    _ops_check(what, [(data, "bytes", (torch.uint8,)), (frame_off, "frame_off", (torch.int64,))] + dicts)
-    if data.dim() != 1 or frame_off.dim() != 1 or frame_off.shape[0] < 1:
-        raise ValueError(f"{what}: bytes must be a uint8 vector and frame_off an int64 (N+1,) tensor")
-    if any(d.dim() != 1 or d.shape[0] == 0 for d, _, _ in dicts):
-        raise ValueError(f"{what}: the dictionaries must be non-empty vectors")
-    return frame_off.shape[0] - 1
-
-
-def _vops_ingest(what, fn, buf_cls, batch_cls, data, frame_off, N, A, dict_args, K2w, sync, caps, ctx):
-    """The sizing call (sync) or the caller's capacities, then the fill: the batch is allocated as the
-    host encoders of map.py leave it (one zero row / id where a pool would be empty)."""
-    ctx = _ctx(data, ctx)
+def _vops_ingest(fn, buf_cls, batch_cls, data, frame_off, N, A, dict_args, K2w, sync, caps, ctx):
+    """The batch is allocated as the host encoders of map.py leave it (one zero row / id where a pool
+    would be empty)."""
     dev = data.device
     has_mem = "mems" in batch_cls._fields
     e = lambda n, dt: torch.empty(n, dtype=dt, device=dev)  # noqa: E731
-    status = e(N, torch.int32)
-    op_off, row_off, key_first = (e(N + 1, torch.int64) for _ in range(3))
-    mem_first = e(N + 1, torch.int64) if has_mem else None
-    head = (_ptr_or_dummy(data), dptr(frame_off), N, *dict_args)
-    firsts = (dptr(row_off), dptr(key_first)) + ((dptr(mem_first),) if has_mem else ())
-    totals = None
-    if sync:
-        tot = (ctypes.c_uint64 * 4)()
-        if N:
-            ctx.call(fn, *head, None, *((None,) * len(firsts)), dptr(status), tot)
-        totals = tuple(int(x) for x in tot)
-        caps = totals
-    n_op, n_row, n_key = caps[:3]
-    n_mem = caps[3] if has_mem else 0
-    t = {}
-    for nm in batch_cls._fields:
-        if nm in ("op_off", "clk_pool", "key_off", "keys", "mem_off", "mems", "ikeys"):
-            continue
-        t[nm] = e(n_op, _VOPS_DTYPES.get(nm, _I64)[0])
-    t["op_off"] = op_off
-    t["clk_pool"] = torch.empty((max(n_row, 1), A), dtype=torch.int64, device=dev)
-    t["key_off"], t["keys"] = e(n_op + 1, torch.int64), e(max(n_key, 1), torch.int32)
-    if has_mem:
-        t["mem_off"], t["mems"] = e(n_op + 1, torch.int64), e(max(n_mem, 1), torch.int32)
-    if "ikeys" in batch_cls._fields:
-        t["ikeys"] = e(n_op, torch.int64) if K2w == 1 else torch.empty((n_op, K2w), dtype=torch.int64, device=dev)
-    if n_row == 0:
-        t["clk_pool"].zero_()
-    if n_key == 0:
-        t["keys"].zero_()
-    if has_mem and n_mem == 0:
-        t["mems"].zero_()
-    b = buf_cls()
-    b.op_cap, b.row_cap, b.key_cap = n_op, n_row, n_key
-    if has_mem:
-        b.mem_cap = n_mem
-    for nm in batch_cls._fields:
-        setattr(b, nm, dptr(t[nm]))
-    if N:
-        ctx.call(fn, *head, ctypes.byref(b), *firsts, dptr(status), None)
-    else:
-        for x in (op_off, row_off, key_first, t["key_off"][:1]) + ((mem_first, t["mem_off"][:1]) if has_mem else ()):
-            x.zero_()
-    return VMapOpsIngest(batch_cls(*(t[nm] for nm in batch_cls._fields)), status, row_off, key_first, mem_first, totals)
+
+    def alloc(caps, op_off):
+        n_op, n_row, n_key = caps[:3]
+        n_mem = caps[3] if has_mem else 0
+        t = {}
+        for nm in batch_cls._fields:
+            if nm in ("op_off", "clk_pool", "key_off", "keys", "mem_off", "mems", "ikeys"):
+                continue
+            t[nm] = e(n_op, _VOPS_DTYPES.get(nm, _I64)[0])
+        t["op_off"] = op_off
+        t["clk_pool"] = torch.empty((max(n_row, 1), A), dtype=torch.int64, device=dev)
+        t["key_off"], t["keys"] = e(n_op + 1, torch.int64), e(max(n_key, 1), torch.int32)
+        if has_mem:
+            t["mem_off"], t["mems"] = e(n_op + 1, torch.int64), e(max(n_mem, 1), torch.int32)
+        if "ikeys" in batch_cls._fields:
+            t["ikeys"] = e(n_op, torch.int64) if K2w == 1 else torch.empty((n_op, K2w), dtype=torch.int64, device=dev)
+        if n_row == 0:
+            t["clk_pool"].zero_()
+        if n_key == 0:
+            t["keys"].zero_()
+        if has_mem and n_mem == 0:
+            t["mems"].zero_()
+        b = buf_cls()
+        b.op_cap, b.row_cap, b.key_cap = n_op, n_row, n_key
+        if has_mem:
+            b.mem_cap = n_mem
+        for nm in batch_cls._fields:
+            setattr(b, nm, dptr(t[nm]))
+        return b, batch_cls(*(t[nm] for nm in batch_cls._fields)), (t["key_off"],) + ((t["mem_off"],) if has_mem else ())
+
+    batch, status, firsts, totals = _sized_ingest(fn, data, frame_off, N, dict_args, 3 if has_mem else 2, 4, sync, caps,
+                                                  alloc, ctx)
+    return VMapOpsIngest(batch, status, firsts[0], firsts[1], firsts[2] if has_mem else None, totals)
 
 
 def map_counter_ops_ingest(data: torch.Tensor, frame_off: torch.Tensor, actors: torch.Tensor, keys: torch.Tensor,
@@ -751,10 +732,10 @@ def map_counter_ops_ingest(data: torch.Tensor, frame_off: torch.Tensor, actors: 
     key_cap), never synchronises, and marks states past a capacity with CAP."""
     from .map import MapCounterOpBatch
     what = "wire.map_counter_ops_ingest"
-    caps = _vops_caps(what, sync, caps, 3)
-    N = _vops_frames(what, data, frame_off, actors, keys)
+    caps = _caps_check(what, sync, caps, _VOPS_CAPS[:3])
+    N = _frames_check(what, data, frame_off, [_d32(actors, "actors"), _d32(keys, "keys")])
     A, K = actors.shape[0], keys.shape[0]
-    return _vops_ingest(what, "crdt_map_counter_ops_ingest", _abi.MapCounterOpsBuf, MapCounterOpBatch, data, frame_off,
+    return _vops_ingest("crdt_map_counter_ops_ingest", _abi.MapCounterOpsBuf, MapCounterOpBatch, data, frame_off,
                         N, A, (dptr(actors), A, dptr(keys), K, 1 if pn else 0), 1, sync, caps, ctx)
 
 
@@ -766,10 +747,11 @@ def map_orswot_ops_ingest(data: torch.Tensor, frame_off: torch.Tensor, actors: t
     caps=(op_cap, row_cap, key_cap, mem_cap))."""
     from .map import MapOrswotOpBatch
     what = "wire.map_orswot_ops_ingest"
-    caps = _vops_caps(what, sync, caps, 4)
-    N = _vops_frames(what, data, frame_off, actors, keys, members, torch.int64, "members")
+    caps = _caps_check(what, sync, caps, _VOPS_CAPS)
+    N = _frames_check(what, data, frame_off, [_d32(actors, "actors"), _d32(keys, "keys"),
+                                              (members, "members", torch.int64)])
     A, K, M = actors.shape[0], keys.shape[0], members.shape[0]
-    return _vops_ingest(what, "crdt_map_orswot_ops_ingest", _abi.MapOrswotOpsBuf, MapOrswotOpBatch, data, frame_off,
+    return _vops_ingest("crdt_map_orswot_ops_ingest", _abi.MapOrswotOpsBuf, MapOrswotOpBatch, data, frame_off,
                         N, A, (dptr(actors), A, dptr(keys), K, dptr(members), M), 1, sync, caps, ctx)
 
 
@@ -786,10 +768,10 @@ def map_nested_ops_ingest(data: torch.Tensor, frame_off: torch.Tensor, actors: t
     past it; sync=False: caps=(op_cap, row_cap, key_cap))."""
     from .map import MapNestedOpBatch
     what = "wire.map_nested_ops_ingest"
-    caps = _vops_caps(what, sync, caps, 3)
-    N = _vops_frames(what, data, frame_off, actors, keys, idict, torch.int32, "idict")
+    caps = _caps_check(what, sync, caps, _VOPS_CAPS[:3])
+    N = _frames_check(what, data, frame_off, [_d32(actors, "actors"), _d32(keys, "keys"), _d32(idict, "idict")])
     A, K, K2 = actors.shape[0], keys.shape[0], idict.shape[0]
-    return _vops_ingest(what, "crdt_map_nested_ops_ingest", _abi.MapNestedOpsBuf, MapNestedOpBatch, data, frame_off,
+    return _vops_ingest("crdt_map_nested_ops_ingest", _abi.MapNestedOpsBuf, MapNestedOpBatch, data, frame_off,
                         N, A, (dptr(actors), A, dptr(keys), K, dptr(idict), K2), _k2w(K2), sync, caps, ctx)
 
 
@@ -830,16 +812,7 @@ def _vops_batch(what, ops, batch_cls, o, actors, keys, third=None, third_dt=None
 
 
 def _vops_egress(fn, o, ops, N, dict_args, ctx):
-    ctx = _ctx(ops.op_off, ctx)
-    dev = ops.op_off.device
-    status = torch.empty(N, dtype=torch.int32, device=dev)
-    frame_off = torch.zeros(N + 1, dtype=torch.int64, device=dev)
-    total = ctypes.c_size_t()
-    args = (ctypes.byref(o), N, *dict_args)
-    ctx.call(fn, *args, dptr(frame_off), None, 0, ctypes.byref(total), dptr(status))
-    data = torch.empty(max(total.value, 1), dtype=torch.uint8, device=dev)
-    ctx.call(fn, *args, dptr(frame_off), dptr(data), data.numel(), ctypes.byref(total), dptr(status))
-    return frame_off, data[:total.value], status
+    return _egress(_ctx(ops.op_off, ctx), fn, N, ops.op_off.device, ctypes.byref(o), N, *dict_args, with_status=True)
 
 
 def map_counter_ops_egress(ops, actors: torch.Tensor, keys: torch.Tensor, pn: bool = False,
@@ -891,16 +864,6 @@ class MVRegOpsIngest(NamedTuple):
     totals: Optional[tuple]   # (ops, rows) of the well-formed frames; None with sync=False
 
 
-def _mvreg_frames(what, data, frame_off, actors):
-    _ops_check(what, ((data, "bytes", (torch.uint8,)), (frame_off, "frame_off", (torch.int64,)),
-                      (actors, "actors", (torch.int32,))))
-    if data.dim() != 1 or frame_off.dim() != 1 or frame_off.shape[0] < 1:
-        raise ValueError(f"{what}: bytes must be a uint8 vector and frame_off an int64 (N+1,) tensor")
-    if actors.dim() != 1 or actors.shape[0] == 0:
-        raise ValueError(f"{what}: the actor dictionary must be a non-empty vector")
-    return frame_off.shape[0] - 1, actors.shape[0]
-
-
 def _mvreg_states(what, vclk, vval, actors):
     for t, nm in ((vclk, "vclk"), (vval, "vval")):  # (registers may be strided: no contiguity asked here)
         if not isinstance(t, torch.Tensor):
@@ -927,7 +890,7 @@ def mvreg_ingest(data: torch.Tensor, frame_off: torch.Tensor, actors: torch.Tens
     values in Vec order from slot 0, the rest zero.  status bits BAD / MISSING / CAP (more than V
     values: the first V kept) / EMPTY_CLOCK (a value with an empty clock: dropped)."""
     what = "wire.mvreg_ingest"
-    N, A = _mvreg_frames(what, data, frame_off, actors)
+    N, A = _frames_check(what, data, frame_off, [_d32(actors, "actors")]), actors.shape[0]
     if int(V) < 1:
         raise ValueError(f"{what}: V >= 1 value slots")
     ctx = _ctx(data, ctx)
@@ -957,35 +920,22 @@ def mvreg_ops_ingest(data: torch.Tensor, frame_off: torch.Tensor, actors: torch.
     capacity with CAP."""
     from .mvreg import MVRegOpBatch
     what = "wire.mvreg_ops_ingest"
-    if sync:
-        if caps is not None:
-            raise ValueError(f"{what}: capacities are chosen by the sizing call unless sync=False")
-    elif caps is None or len(caps) != 2 or any(int(c) < 0 for c in caps):
-        raise ValueError(f"{what}: sync=False needs caps=(op_cap, row_cap)")
-    N, A = _mvreg_frames(what, data, frame_off, actors)
-    ctx = _ctx(data, ctx)
+    caps = _caps_check(what, sync, caps, ("op_cap", "row_cap"))
+    N, A = _frames_check(what, data, frame_off, [_d32(actors, "actors")]), actors.shape[0]
     dev = data.device
-    status = torch.empty(N, dtype=torch.int32, device=dev)
-    op_off = torch.empty(N + 1, dtype=torch.int64, device=dev)
-    head = (_ptr_or_dummy(data), dptr(frame_off), N, dptr(actors), A)
-    totals = None
-    if sync:  # size, then fill with exactly enough room (+ one pad row, as encode_ops leaves)
-        tot = (ctypes.c_uint64 * 2)()
-        if N:
-            ctx.call("crdt_mvreg_ops_ingest", *head, None, dptr(status), tot)
-        totals = (int(tot[0]), int(tot[1]))
-        caps = totals
-    n_op, n_row = int(caps[0]), int(caps[1])
-    row = torch.empty(n_op, dtype=torch.int32, device=dev)
-    val = torch.empty(n_op, dtype=torch.int64, device=dev)
-    pool = torch.empty((n_row + 1, A), dtype=torch.int64, device=dev)
-    pool[n_row].zero_()
-    b = _abi.MVRegOpsBuf(n_op, dptr(op_off), dptr(row), dptr(pool), n_row, dptr(val))
-    if N:
-        ctx.call("crdt_mvreg_ops_ingest", *head, ctypes.byref(b), dptr(status), None)
-    else:
-        op_off.zero_()
-    return MVRegOpsIngest(MVRegOpBatch(op_off, row, pool, val), status, totals)
+
+    def alloc(caps, op_off):  # exactly enough room + one pad row, as encode_ops leaves
+        n_op, n_row = caps
+        row = torch.empty(n_op, dtype=torch.int32, device=dev)
+        val = torch.empty(n_op, dtype=torch.int64, device=dev)
+        pool = torch.empty((n_row + 1, A), dtype=torch.int64, device=dev)
+        pool[n_row].zero_()
+        b = _abi.MVRegOpsBuf(n_op, dptr(op_off), dptr(row), dptr(pool), n_row, dptr(val))
+        return b, MVRegOpBatch(op_off, row, pool, val), ()
+
+    ops, status, _, totals = _sized_ingest("crdt_mvreg_ops_ingest", data, frame_off, N, (dptr(actors), A), 0, 2, sync, caps,
+                                           alloc, ctx)
+    return MVRegOpsIngest(ops, status, totals)
 
 
 def mvreg_ops_egress(ops, actors: torch.Tensor, ctx: Optional[Context] = None):
@@ -1007,17 +957,8 @@ def mvreg_ops_egress(ops, actors: torch.Tensor, ctx: Optional[Context] = None):
     N = ops.op_off.shape[0] - 1
     o = _abi.MVRegOps(n, dptr(ops.op_off), _ptr_or_dummy(ops.clk_row), _ptr_or_dummy(ops.clk_pool),
                       ops.clk_pool.shape[0], _ptr_or_dummy(ops.val))
-    ctx = _ctx(ops.op_off, ctx)
-    dev = ops.op_off.device
-    status = torch.empty(N, dtype=torch.int32, device=dev)
-    args = (ctypes.byref(o), N, dptr(actors), actors.shape[0])
-    frame_off = torch.zeros(N + 1, dtype=torch.int64, device=dev)
-    total = ctypes.c_size_t()
-    ctx.call("crdt_mvreg_ops_egress", *args, dptr(frame_off), None, 0, ctypes.byref(total), dptr(status))
-    data = torch.empty(max(total.value, 1), dtype=torch.uint8, device=dev)
-    ctx.call("crdt_mvreg_ops_egress", *args, dptr(frame_off), dptr(data), data.numel(), ctypes.byref(total),
-             dptr(status))
-    return frame_off, data[:total.value], status
+    return _egress(_ctx(ops.op_off, ctx), "crdt_mvreg_ops_egress", N, ops.op_off.device, ctypes.byref(o), N, dptr(actors),
+                   actors.shape[0], with_status=True)
 
 
 # ---- the lattice types' op streams (include/crdt_gpu.h "the lattice types' op streams") --------------
@@ -1049,58 +990,27 @@ class LwwRegOpsIngest(NamedTuple):
     totals: Optional[tuple]
 
 
-def _lops_caps(what, sync, caps):
-    if sync:
-        if caps is not None:
-            raise ValueError(f"{what}: capacities are chosen by the sizing call unless sync=False")
-        return None
-    if caps is None or len(caps) != 1 or int(caps[0]) < 0:
-        raise ValueError(f"{what}: sync=False needs caps=(op_cap,)")
-    return int(caps[0])
-
-
-def _lops_frames(what, data, frame_off, d=None, d_dt=None, d_nm=None):
-    ts = [(data, "bytes", (torch.uint8,)), (frame_off, "frame_off", (torch.int64,))]
-    if d_nm:
-        ts.append((d, d_nm, (d_dt,)))
-    _ops_check(what, ts)
-    if data.dim() != 1 or frame_off.dim() != 1 or frame_off.shape[0] < 1:
-        raise ValueError(f"{what}: bytes must be a uint8 vector and frame_off an int64 (N+1,) tensor")
-    if d_nm and (d.dim() != 1 or d.shape[0] == 0):
-        raise ValueError(f"{what}: the {d_nm} dictionary must be a non-empty vector")
-    return frame_off.shape[0] - 1
-
-
 def _dot_ops_ingest(what, kind, data, frame_off, d, d_dt, d_nm, sync, caps, ctx):
-    cap = _lops_caps(what, sync, caps)
-    N = _lops_frames(what, data, frame_off, d, d_dt, d_nm)
-    fn = f"crdt_{kind}_ops_ingest"
-    ctx = _ctx(data, ctx)
+    caps = _caps_check(what, sync, caps, ("op_cap",))
+    N = _frames_check(what, data, frame_off, [(d, d_nm, d_dt)])
     dev = data.device
-    status = torch.empty(N, dtype=torch.int32, device=dev)
-    op_off = torch.empty(N + 1, dtype=torch.int64, device=dev)
-    head = (_ptr_or_dummy(data), dptr(frame_off), N, dptr(d), d.shape[0])
-    totals = None
-    if sync:
-        tot = (ctypes.c_uint64 * 1)()
-        if N:
-            ctx.call(fn, *head, None, dptr(status), tot)
-        totals = (int(tot[0]),)
-        cap = totals[0]
-    if sync:
-        state_idx = torch.empty(cap, dtype=torch.int32, device=dev)
-    else:  # entries past the ops kept are never written: an apply of the whole arrays skips them
-        state_idx = torch.full((cap,), -1, dtype=torch.int32, device=dev)
-    col = torch.empty(cap, dtype=torch.int32, device=dev)
-    counter = torch.empty(cap, dtype=torch.int64, device=dev) if kind != "gset" else None
-    dr = torch.empty(cap, dtype=torch.uint8, device=dev) if kind == "pncounter" else None
-    b = _abi.DotOpsBuf(cap, dptr(op_off), _ptr_or_dummy(state_idx), _ptr_or_dummy(col),
-                       None if counter is None else _ptr_or_dummy(counter), None if dr is None else _ptr_or_dummy(dr))
-    if N:
-        ctx.call(fn, *head, ctypes.byref(b), dptr(status), None)
-    else:
-        op_off.zero_()
-    return DotOpsIngest(DotOpBatch(op_off, state_idx, col, counter, dr), status, totals)
+
+    def alloc(caps, op_off):
+        (cap,) = caps
+        if sync:
+            state_idx = torch.empty(cap, dtype=torch.int32, device=dev)
+        else:  # entries past the ops kept are never written: an apply of the whole arrays skips them
+            state_idx = torch.full((cap,), -1, dtype=torch.int32, device=dev)
+        col = torch.empty(cap, dtype=torch.int32, device=dev)
+        counter = torch.empty(cap, dtype=torch.int64, device=dev) if kind != "gset" else None
+        dr = torch.empty(cap, dtype=torch.uint8, device=dev) if kind == "pncounter" else None
+        b = _abi.DotOpsBuf(cap, dptr(op_off), _ptr_or_dummy(state_idx), _ptr_or_dummy(col),
+                           None if counter is None else _ptr_or_dummy(counter), None if dr is None else _ptr_or_dummy(dr))
+        return b, DotOpBatch(op_off, state_idx, col, counter, dr), ()
+
+    ops, status, _, totals = _sized_ingest(f"crdt_{kind}_ops_ingest", data, frame_off, N, (dptr(d), d.shape[0]), 0, 1, sync,
+                                           caps, alloc, ctx)
+    return DotOpsIngest(ops, status, totals)
 
 
 def vclock_ops_ingest(data: torch.Tensor, frame_off: torch.Tensor, actors: torch.Tensor, sync: bool = True, caps=None,
@@ -1134,38 +1044,19 @@ def lwwreg_ops_ingest(data: torch.Tensor, frame_off: torch.Tensor, sync: bool = 
     lwwreg.LwwRegOpBatch; 16-byte records (val, marker), no dictionary."""
     from .lwwreg import LwwRegOpBatch
     what = "wire.lwwreg_ops_ingest"
-    cap = _lops_caps(what, sync, caps)
-    N = _lops_frames(what, data, frame_off)
-    ctx = _ctx(data, ctx)
+    caps = _caps_check(what, sync, caps, ("op_cap",))
+    N = _frames_check(what, data, frame_off, [])
     dev = data.device
-    status = torch.empty(N, dtype=torch.int32, device=dev)
-    op_off = torch.empty(N + 1, dtype=torch.int64, device=dev)
-    head = (_ptr_or_dummy(data), dptr(frame_off), N)
-    totals = None
-    if sync:
-        tot = (ctypes.c_uint64 * 1)()
-        if N:
-            ctx.call("crdt_lwwreg_ops_ingest", *head, None, dptr(status), tot)
-        totals = (int(tot[0]),)
-        cap = totals[0]
-    marker = torch.empty(cap, dtype=torch.int64, device=dev)
-    val = torch.empty(cap, dtype=torch.int64, device=dev)
-    b = _abi.LwwRegOpsBuf(cap, dptr(op_off), _ptr_or_dummy(marker), _ptr_or_dummy(val))
-    if N:
-        ctx.call("crdt_lwwreg_ops_ingest", *head, ctypes.byref(b), dptr(status), None)
-    else:
-        op_off.zero_()
-    return LwwRegOpsIngest(LwwRegOpBatch(op_off, marker, val), status, totals)
 
+    def alloc(caps, op_off):
+        (cap,) = caps
+        marker = torch.empty(cap, dtype=torch.int64, device=dev)
+        val = torch.empty(cap, dtype=torch.int64, device=dev)
+        b = _abi.LwwRegOpsBuf(cap, dptr(op_off), _ptr_or_dummy(marker), _ptr_or_dummy(val))
+        return b, LwwRegOpBatch(op_off, marker, val), ()
 
-def _lops_egress(ctx, fn, N, dev, *args):
-    status = torch.empty(N, dtype=torch.int32, device=dev)
-    frame_off = torch.zeros(N + 1, dtype=torch.int64, device=dev)
-    total = ctypes.c_size_t()
-    ctx.call(fn, *args, dptr(frame_off), None, 0, ctypes.byref(total), dptr(status))
-    data = torch.empty(max(total.value, 1), dtype=torch.uint8, device=dev)
-    ctx.call(fn, *args, dptr(frame_off), dptr(data), data.numel(), ctypes.byref(total), dptr(status))
-    return frame_off, data[:total.value], status
+    ops, status, _, totals = _sized_ingest("crdt_lwwreg_ops_ingest", data, frame_off, N, (), 0, 1, sync, caps, alloc, ctx)
+    return LwwRegOpsIngest(ops, status, totals)
 
 
 def _dot_ops_egress(what, kind, ops, d, d_dt, d_nm, ctx):
@@ -1188,8 +1079,8 @@ def _dot_ops_egress(what, kind, ops, d, d_dt, d_nm, ctx):
     o = _abi.DotOps(n, dptr(ops.op_off), None, _ptr_or_dummy(ops.actor),
                     None if kind == "gset" else _ptr_or_dummy(ops.counter),
                     _ptr_or_dummy(ops.dir) if kind == "pncounter" else None)
-    ctx = _ctx(ops.op_off, ctx)
-    return _lops_egress(ctx, f"crdt_{kind}_ops_egress", N, ops.op_off.device, ctypes.byref(o), N, dptr(d), d.shape[0])
+    return _egress(_ctx(ops.op_off, ctx), f"crdt_{kind}_ops_egress", N, ops.op_off.device, ctypes.byref(o), N, dptr(d),
+                   d.shape[0], with_status=True)
 
 
 def vclock_ops_egress(ops, actors: torch.Tensor, ctx: Optional[Context] = None):
@@ -1222,5 +1113,5 @@ def lwwreg_ops_egress(ops, ctx: Optional[Context] = None):
         raise ValueError(f"{what}: op_off (N+1,) and marker / val (n_ops,) expected")
     N = ops.op_off.shape[0] - 1
     o = _abi.LwwRegOps(n, dptr(ops.op_off), _ptr_or_dummy(ops.marker), _ptr_or_dummy(ops.val))
-    ctx = _ctx(ops.op_off, ctx)
-    return _lops_egress(ctx, "crdt_lwwreg_ops_egress", N, ops.op_off.device, ctypes.byref(o), N)
+    return _egress(_ctx(ops.op_off, ctx), "crdt_lwwreg_ops_egress", N, ops.op_off.device, ctypes.byref(o), N,
+                   with_status=True)

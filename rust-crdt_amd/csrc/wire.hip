@@ -27,7 +27,7 @@
 // position in the dictionary.  Ingest is one wave per state: the record loop runs across lanes
 // (lane i parses record i), rows are assembled in LDS and written out with coalesced stores.
 // Egress is count -> exclusive scan -> write.
-#include "wire_common.hpp"
+#include "wire_driver.hpp"
 
 namespace crdt {
 
@@ -1549,45 +1549,49 @@ int crdt_orswot_ingest(crdt_ctx *ctx, const uint8_t *bytes, const uint64_t *fram
   if ((dw + wpb * (A + Mw)) * 8 <= 64 * 1024) p.dict_words = dw;
   const unsigned grid = wave_grid(ctx, N, wpb, 32);
   timing_begin(ctx, "wire_ingest");
-  // pass 1: walk + batched parse (wwalk=1, default), the dictionaries in LDS when they fit beside
-  // sixteen 4-KiB frame rings; else the one-chain kernel
-  const size_t ring_w = (size_t)kOrWalkRing * kWalkWin / 2;
-  const size_t walk_lds = (dw + kOrWalkWaves * ring_w) * 8;
-  const size_t fill_lds = (dw + (kOfWalk + 1) / 2 + kOfWalk * ring_w) * 8;
-  if (ctx->tune.wire_walk && ctx->tune.wire_fill && fill_lds <= 80 * 1024 && N * M <= 0xffffffffffull &&
-      N * M * A * 8 > 0) {
-    // zero rows by filler waves beside the walk (no separate fill pass); two blocks per CU
-    if (int rc = ensure_scratch(ctx, (2 * N + nb + 8) * 8 + N * M * 4)) return rc;
-    dpos = reinterpret_cast<u64 *>(ctx->scratch), dcount = dpos + N, sc = dcount + N;
-    p.dpos = dpos;
-    p.dcount = dcount;
-    IngestPlan q = p;
-    q.dict_words = dw;
-    uint32_t *epos = reinterpret_cast<uint32_t *>(sc + nb + 8);
-    CRDT_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&orswot_ingest_walk_fill_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)fill_lds));
-    hipLaunchKernelGGL(orswot_ingest_walk_fill_kernel, dim3((unsigned)((N + kOfWalk - 1) / kOfWalk)),
-                       dim3((kOfWalk + kOfFill) * kWave), fill_lds, ctx->stream, q, epos);
-  } else if (ctx->tune.wire_walk && walk_lds <= 160 * 1024) {
-    if (int rc = device_fill(ctx, entries, N * M * A * 8, 0)) return rc;
-    IngestPlan q = p;
-    q.dict_words = dw;
-    CRDT_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&orswot_ingest_walk_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)walk_lds));
-    hipLaunchKernelGGL(orswot_ingest_walk_kernel, dim3(wave_grid(ctx, N, kOrWalkWaves, 8)),
-                       dim3(kOrWalkWaves * kWave), walk_lds, ctx->stream, q);
-  } else {
-    if (int rc = device_fill(ctx, entries, N * M * A * 8, 0)) return rc;
-    hipLaunchKernelGGL(orswot_ingest_kernel, dim3(grid), dim3(wpb * kWave), (p.dict_words + wpb * A) * 8, ctx->stream, p);
-  }
-  CRDT_HIP(ctx, hipGetLastError());
   unsigned long long D = 0;
-  if (int rc = exclusive_scan(ctx, dcount, (u64 *)def_off, N, sc, &D)) return rc;
-  if (D)
-    hipLaunchKernelGGL(orswot_ingest_deferred_kernel, dim3(grid), dim3(wpb * kWave),
-                       (p.dict_words + wpb * (A + Mw)) * 8, ctx->stream, p);
+  const int rc = [&]() -> int {  // (every return in here passes timing_end: no timing entry without its stop event)
+    // pass 1: walk + batched parse (wwalk=1, default), the dictionaries in LDS when they fit beside
+    // sixteen 4-KiB frame rings; else the one-chain kernel
+    const size_t ring_w = (size_t)kOrWalkRing * kWalkWin / 2;
+    const size_t walk_lds = (dw + kOrWalkWaves * ring_w) * 8;
+    const size_t fill_lds = (dw + (kOfWalk + 1) / 2 + kOfWalk * ring_w) * 8;
+    if (ctx->tune.wire_walk && ctx->tune.wire_fill && fill_lds <= 80 * 1024 && N * M <= 0xffffffffffull &&
+        N * M * A * 8 > 0) {
+      // zero rows by filler waves beside the walk (no separate fill pass); two blocks per CU
+      if (int rc = ensure_scratch(ctx, (2 * N + nb + 8) * 8 + N * M * 4)) return rc;
+      dpos = reinterpret_cast<u64 *>(ctx->scratch), dcount = dpos + N, sc = dcount + N;
+      p.dpos = dpos;
+      p.dcount = dcount;
+      IngestPlan q = p;
+      q.dict_words = dw;
+      uint32_t *epos = reinterpret_cast<uint32_t *>(sc + nb + 8);
+      CRDT_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&orswot_ingest_walk_fill_kernel),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)fill_lds));
+      hipLaunchKernelGGL(orswot_ingest_walk_fill_kernel, dim3((unsigned)((N + kOfWalk - 1) / kOfWalk)),
+                         dim3((kOfWalk + kOfFill) * kWave), fill_lds, ctx->stream, q, epos);
+    } else if (ctx->tune.wire_walk && walk_lds <= 160 * 1024) {
+      if (int rc = device_fill(ctx, entries, N * M * A * 8, 0)) return rc;
+      IngestPlan q = p;
+      q.dict_words = dw;
+      CRDT_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&orswot_ingest_walk_kernel),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)walk_lds));
+      hipLaunchKernelGGL(orswot_ingest_walk_kernel, dim3(wave_grid(ctx, N, kOrWalkWaves, 8)),
+                         dim3(kOrWalkWaves * kWave), walk_lds, ctx->stream, q);
+    } else {
+      if (int rc = device_fill(ctx, entries, N * M * A * 8, 0)) return rc;
+      hipLaunchKernelGGL(orswot_ingest_kernel, dim3(grid), dim3(wpb * kWave), (p.dict_words + wpb * A) * 8, ctx->stream, p);
+    }
+    CRDT_HIP(ctx, hipGetLastError());
+    if (int rc = exclusive_scan(ctx, dcount, (u64 *)def_off, N, sc, &D)) return rc;
+    if (D)
+      hipLaunchKernelGGL(orswot_ingest_deferred_kernel, dim3(grid), dim3(wpb * kWave),
+                         (p.dict_words + wpb * (A + Mw)) * 8, ctx->stream, p);
+    CRDT_HIP(ctx, hipGetLastError());
+    return CRDT_OK;
+  }();
   timing_end(ctx);
-  CRDT_HIP(ctx, hipGetLastError());
+  if (rc) return rc;
   if (n_def) *n_def = D;
   return CRDT_OK;
 }
@@ -1683,23 +1687,8 @@ int crdt_map_egress(crdt_ctx *ctx, const crdt_map_states *states, const crdt_map
   const size_t N = p.N;
   if (N == 0) return CRDT_OK;
   if (!frame_off || !total) return fail(ctx, CRDT_EINVAL, "map_egress: need frame_off and total");
-  CRDT_HIP(ctx, hipSetDevice(ctx->device));
-  u64 *sizes = nullptr;
-  if (int rc = wire_scratch(ctx, N, &sizes)) return rc;
-  p.sizes = sizes;
-  const unsigned grid = wave_grid(ctx, N, 4, 32);
-  timing_begin(ctx, "wire_egress");
-  hipLaunchKernelGGL(map_egress_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, p, 0);
-  CRDT_HIP(ctx, hipGetLastError());
-  if (int rc = egress_layout(ctx, sizes, (u64 *)frame_off, N, total)) return rc;
-  if (bytes && cap >= *total) {
-    p.frame_out = (const u64 *)frame_off;
-    p.out = bytes;
-    hipLaunchKernelGGL(map_egress_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, p, 1);
-    CRDT_HIP(ctx, hipGetLastError());
-  }
-  timing_end(ctx);
-  return CRDT_OK;
+  return two_pass_egress(ctx, "wire_egress", map_egress_kernel, p, wave_grid(ctx, N, 4, 32), frame_off, bytes, cap, total,
+                         StatePlanOut{});
 }
 
 static int egress_common(crdt_ctx *ctx, EgressPlan p, size_t N, uint64_t *frame_off, uint8_t *bytes, size_t cap,
@@ -1708,23 +1697,7 @@ static int egress_common(crdt_ctx *ctx, EgressPlan p, size_t N, uint64_t *frame_
   if (total) *total = 0;
   if (N == 0) return CRDT_OK;
   if (!frame_off || !total) return fail(ctx, CRDT_EINVAL, "%s: need frame_off and total", what);
-  CRDT_HIP(ctx, hipSetDevice(ctx->device));
-  u64 *sizes = nullptr;
-  if (int rc = wire_scratch(ctx, N, &sizes)) return rc;
-  p.sizes = sizes;
-  const unsigned grid = wave_grid(ctx, N, 4, 32);
-  timing_begin(ctx, "wire_egress");
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, ctx->stream, p, 0);
-  CRDT_HIP(ctx, hipGetLastError());
-  if (int rc = egress_layout(ctx, sizes, (u64 *)frame_off, N, total)) return rc;
-  if (bytes && cap >= *total) {
-    p.frame_off = (const u64 *)frame_off;
-    p.bytes = bytes;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, ctx->stream, p, 1);
-    CRDT_HIP(ctx, hipGetLastError());
-  }
-  timing_end(ctx);
-  return CRDT_OK;
+  return two_pass_egress(ctx, "wire_egress", kern, p, wave_grid(ctx, N, 4, 32), frame_off, bytes, cap, total);
 }
 
 int crdt_vclock_egress(crdt_ctx *ctx, const uint64_t *rows, size_t N, size_t A, size_t row_stride,

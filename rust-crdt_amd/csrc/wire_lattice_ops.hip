@@ -22,8 +22,8 @@
 // Egress: count (validate, frame sizes) -> scan -> write, a wave per state, lane = op.
 // One kernel template over the record kind serves the four streams.  (Fixed-width records put op i of a
 // state at op_off + i, so neither the op-stream walk nor the in-wave prefix sum of wire_ops_common.hpp
-// is needed: the exclusive scan over states and the egress layout of wire_common.hpp are.)
-#include "wire_common.hpp"
+// is needed: the sized ingest and the two-pass egress of wire_driver.hpp are.)
+#include "wire_driver.hpp"
 
 namespace crdt {
 
@@ -100,22 +100,6 @@ __global__ __launch_bounds__(kBlock) void lops_count_kernel(LopsPlan p) {
       p.counts[s] = ok ? n : 0;
     }
   }
-}
-
-// raw [N+1]: the scan of the counts.  The first state whose ops end past the capacity and every one
-// after it get bit 2 and no room (the prefix cut of crdt_orswot_ops_ingest).
-__global__ __launch_bounds__(kBlock) void lops_finalize_kernel(const u64 *raw, unsigned long long N, u64 cap, u64 *op_off,
-                                                               uint32_t *status) {
-  const unsigned long long i = blockIdx.x * (unsigned long long)kBlock + threadIdx.x;
-  if (i > N) return;
-  unsigned long long lo = 0, hi = N;  // raw ascends
-  while (lo < hi) {
-    const unsigned long long mid = (lo + hi) / 2;
-    if (raw[mid + 1] > cap) hi = mid;
-    else lo = mid + 1;
-  }
-  op_off[i] = raw[i < lo ? i : lo];
-  if (i < N && i >= lo) status[i] |= kWireCap;
 }
 
 template <int KIND>
@@ -233,38 +217,21 @@ __global__ __launch_bounds__(kBlock) void lops_egress_kernel(LopsEgressPlan p, i
 
 template <int KIND>
 static int lops_ingest(crdt_ctx *ctx, const char *what, LopsPlan &p, u64 cap, bool fill, u64 *op_off, uint64_t *totals) {
-  const unsigned long long N = p.N;
-  CRDT_HIP(ctx, hipSetDevice(ctx->device));
-  // scratch: counts [N] | raw offsets [N+1] | scan scratch
-  const unsigned long long nb = (N + kScanItems - 1) / kScanItems + 2;
-  if (int rc = ensure_scratch(ctx, (N + (N + 1) + nb + 8) * 8)) return rc;
-  u64 *counts = reinterpret_cast<u64 *>(ctx->scratch), *raw = counts + N, *sc = raw + (N + 1);
-  p.counts = counts;
-  timing_begin(ctx, what);
-  int rc = CRDT_OK;
-  hipLaunchKernelGGL(lops_count_kernel<KIND>, dim3(wave_grid(ctx, (N + kWave - 1) / kWave, kLopWpb, 32)), dim3(kBlock), 0,
-                     ctx->stream, p);
-  if (hipGetLastError() != hipSuccess) rc = fail(ctx, CRDT_EHIP, "%s: count launch", what);
-  if (!rc) rc = exclusive_scan(ctx, counts, raw, N, sc, nullptr);
-  if (!rc && fill) {
-    hipLaunchKernelGGL(lops_finalize_kernel, dim3((unsigned)((N + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream,
-                       (const u64 *)raw, N, cap, op_off, p.status);
-    p.op_off = op_off;
-    const size_t dict_bytes = KIND == kLopLww ? 0 : p.D * (KIND == kLopGset ? 8 : 4);
-    p.stage = dict_bytes <= kLopDictLds;
-    hipLaunchKernelGGL(lops_fill_kernel<KIND>, dim3(wave_grid(ctx, N, kLopWpb, 32)), dim3(kBlock),
-                       p.stage ? (dict_bytes + 7) / 8 * 8 : 0, ctx->stream, p);
-    if (hipGetLastError() != hipSuccess) rc = fail(ctx, CRDT_EHIP, "%s: fill launch", what);
-  }
-  timing_end(ctx);
-  if (rc) return rc;
-  if (totals) {
-    u64 t = 0;
-    CRDT_HIP(ctx, hipMemcpyAsync(&t, raw + N, 8, hipMemcpyDeviceToHost, ctx->stream));
-    CRDT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    totals[0] = t;
-  }
-  return CRDT_OK;
+  const SizedOut<1> o{{cap}, {op_off}, {nullptr, nullptr}, p.status};
+  return sized_ingest<1>(
+      ctx, what, p.N, o, fill, totals,
+      [&](u64 *counts) {
+        p.counts = counts;
+        hipLaunchKernelGGL(lops_count_kernel<KIND>, dim3(wave_grid(ctx, (p.N + kWave - 1) / kWave, kLopWpb, 32)), dim3(kBlock),
+                           0, ctx->stream, p);
+      },
+      [&] {
+        p.op_off = op_off;
+        const size_t dict_bytes = KIND == kLopLww ? 0 : p.D * (KIND == kLopGset ? 8 : 4);
+        p.stage = dict_bytes <= kLopDictLds;
+        hipLaunchKernelGGL(lops_fill_kernel<KIND>, dim3(wave_grid(ctx, p.N, kLopWpb, 32)), dim3(kBlock),
+                           p.stage ? (dict_bytes + 7) / 8 * 8 : 0, ctx->stream, p);
+      });
 }
 
 // The shared front of the three dictionary-typed ingests.
@@ -297,27 +264,10 @@ static int dot_ops_ingest(crdt_ctx *ctx, const char *what, const uint8_t *bytes,
   return lops_ingest<KIND>(ctx, what, p, out ? out->op_cap : 0, out != nullptr, out ? (u64 *)out->op_off : nullptr, totals);
 }
 
-template <int KIND, class Plan>
-static int lops_egress(crdt_ctx *ctx, const char *what, Plan &p, uint64_t *frame_off, uint8_t *bytes, size_t cap,
+template <int KIND>
+static int lops_egress(crdt_ctx *ctx, const char *what, LopsEgressPlan &p, uint64_t *frame_off, uint8_t *bytes, size_t cap,
                        size_t *total) {
-  const unsigned long long N = p.N;
-  CRDT_HIP(ctx, hipSetDevice(ctx->device));
-  u64 *sizes = nullptr;
-  if (int rc = wire_scratch(ctx, N, &sizes)) return rc;
-  p.sizes = sizes;
-  const unsigned grid = wave_grid(ctx, N, kLopWpb, 32);
-  timing_begin(ctx, what);
-  hipLaunchKernelGGL(lops_egress_kernel<KIND>, dim3(grid), dim3(kBlock), 0, ctx->stream, p, 0);
-  int rc = hipGetLastError() == hipSuccess ? CRDT_OK : fail(ctx, CRDT_EHIP, "%s: count launch", what);
-  if (!rc) rc = egress_layout(ctx, sizes, (u64 *)frame_off, N, total);
-  if (!rc && bytes && cap >= *total) {
-    p.frame_off = (const u64 *)frame_off;
-    p.bytes = bytes;
-    hipLaunchKernelGGL(lops_egress_kernel<KIND>, dim3(grid), dim3(kBlock), 0, ctx->stream, p, 1);
-    if (hipGetLastError() != hipSuccess) rc = fail(ctx, CRDT_EHIP, "%s: write launch", what);
-  }
-  timing_end(ctx);
-  return rc;
+  return two_pass_egress(ctx, what, lops_egress_kernel<KIND>, p, wave_grid(ctx, p.N, kLopWpb, 32), frame_off, bytes, cap, total);
 }
 
 template <int KIND>

@@ -187,22 +187,6 @@ __global__ __launch_bounds__(kBlock) void mvops_count_kernel(MvOpsPlan p) {
   }
 }
 
-// raw [N+1]: the scan of the counts.  The first register whose ops end past the capacity (ops and
-// rows are the same number: the smaller of the two) and every one after it get bit 2 and no room.
-__global__ __launch_bounds__(kBlock) void mvops_finalize_kernel(const u64 *raw, unsigned long long N, u64 cap, u64 *op_off,
-                                                                uint32_t *status) {
-  const unsigned long long i = blockIdx.x * (unsigned long long)kBlock + threadIdx.x;
-  if (i > N) return;
-  unsigned long long lo = 0, hi = N;  // raw ascends
-  while (lo < hi) {
-    const unsigned long long mid = (lo + hi) / 2;
-    if (raw[mid + 1] > cap) hi = mid;
-    else lo = mid + 1;
-  }
-  op_off[i] = raw[i < lo ? i : lo];
-  if (i < N && i >= lo) status[i] |= kWireCap;
-}
-
 __global__ __launch_bounds__(kBlock) void mvops_fill_kernel(MvOpsPlan p) {
   extern __shared__ u64 lds[];
   const int lane = threadIdx.x % kWave, wib = threadIdx.x / kWave;
@@ -374,26 +358,6 @@ static int mv_wire_plan(crdt_ctx *ctx, const crdt_mvreg_states *st, const uint32
   return CRDT_OK;
 }
 
-// The launches of one op ingest, between the caller's timing_begin / timing_end.
-static int mvops_ingest_launch(crdt_ctx *ctx, MvOpsPlan &p, u64 *raw, u64 *sc, u64 cap, bool fill, u64 *op_off) {
-  const unsigned long long N = p.N;
-  const size_t ring_bytes = (size_t)kMvWpb * kWalkRing * kWalkWin * 4;
-  const unsigned grid = wave_grid(ctx, N, kMvWpb, 8);
-  hipLaunchKernelGGL(mvops_count_kernel, dim3(grid), dim3(kBlock), ring_bytes, ctx->stream, p);
-  CRDT_HIP(ctx, hipGetLastError());
-  if (int rc = exclusive_scan(ctx, p.counts, raw, N, sc, nullptr)) return rc;
-  if (!fill) return CRDT_OK;
-  hipLaunchKernelGGL(mvops_finalize_kernel, dim3((unsigned)((N + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream,
-                     (const u64 *)raw, N, cap, op_off, p.status);
-  CRDT_HIP(ctx, hipGetLastError());
-  p.op_off = op_off;
-  const unsigned long long dw = (p.A + 1) / 2;
-  p.dict_words = dw * 8 + ring_bytes <= kMvLdsMax ? dw : 0;  // else: searched in global memory
-  hipLaunchKernelGGL(mvops_fill_kernel, dim3(grid), dim3(kBlock), ring_bytes + p.dict_words * 8, ctx->stream, p);
-  CRDT_HIP(ctx, hipGetLastError());
-  return CRDT_OK;
-}
-
 }  // namespace crdt
 
 using namespace crdt;
@@ -435,23 +399,8 @@ int crdt_mvreg_egress(crdt_ctx *ctx, const crdt_mvreg_states *states, const uint
   const size_t N = p.N;
   if (N == 0) return CRDT_OK;
   if (!frame_off || !total) return fail(ctx, CRDT_EINVAL, "mvreg_egress: need frame_off and total");
-  CRDT_HIP(ctx, hipSetDevice(ctx->device));
-  u64 *sizes = nullptr;
-  if (int rc = wire_scratch(ctx, N, &sizes)) return rc;
-  p.sizes = sizes;
-  const unsigned grid = wave_grid(ctx, N, kMvWpb, 32);
-  timing_begin(ctx, "wire_mvreg_egress");
-  hipLaunchKernelGGL(mvreg_egress_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, p, 0);
-  int rc = hipGetLastError() == hipSuccess ? CRDT_OK : fail(ctx, CRDT_EHIP, "mvreg_egress: count launch");
-  if (!rc) rc = egress_layout(ctx, sizes, (u64 *)frame_off, N, total);
-  if (!rc && bytes && cap >= *total) {
-    p.frame_out = (const u64 *)frame_off;
-    p.out = bytes;
-    hipLaunchKernelGGL(mvreg_egress_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, p, 1);
-    if (hipGetLastError() != hipSuccess) rc = fail(ctx, CRDT_EHIP, "mvreg_egress: write launch");
-  }
-  timing_end(ctx);
-  return rc;
+  return two_pass_egress(ctx, "wire_mvreg_egress", mvreg_egress_kernel, p, wave_grid(ctx, N, kMvWpb, 32), frame_off, bytes, cap,
+                         total, StatePlanOut{});
 }
 
 int crdt_mvreg_ops_ingest(crdt_ctx *ctx, const uint8_t *bytes, const uint64_t *frame_off, size_t N,
@@ -481,23 +430,26 @@ int crdt_mvreg_ops_ingest(crdt_ctx *ctx, const uint8_t *bytes, const uint64_t *f
     p.val = (u64 *)out->val;
     cap = std::min<u64>(out->op_cap, out->row_cap);
   }
-  CRDT_HIP(ctx, hipSetDevice(ctx->device));
-  // scratch: counts [N] | raw offsets [N+1] | scan scratch
-  const unsigned long long nb = (N + kScanItems - 1) / kScanItems + 2;
-  if (int rc = ensure_scratch(ctx, (N + (N + 1) + nb + 8) * 8)) return rc;
-  u64 *counts = reinterpret_cast<u64 *>(ctx->scratch), *raw = counts + N, *sc = raw + (N + 1);
-  p.counts = counts;
-  timing_begin(ctx, "wire_mvreg_ops_ingest");
-  const int rc = mvops_ingest_launch(ctx, p, raw, sc, cap, out != nullptr, out ? (u64 *)out->op_off : nullptr);
-  timing_end(ctx);
-  if (rc) return rc;
-  if (totals) {
-    u64 t = 0;
-    CRDT_HIP(ctx, hipMemcpyAsync(&t, raw + N, 8, hipMemcpyDeviceToHost, ctx->stream));
-    CRDT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    totals[0] = totals[1] = t;
-  }
-  return CRDT_OK;
+  // ops and rows are one number: the smaller capacity binds, and both totals are that count
+  const size_t ring_bytes = (size_t)kMvWpb * kWalkRing * kWalkWin * 4;
+  const unsigned grid = wave_grid(ctx, N, kMvWpb, 8);
+  u64 *op_off = out ? (u64 *)out->op_off : nullptr;
+  const SizedOut<1> o{{cap}, {op_off}, {nullptr, nullptr}, status};
+  uint64_t n_ops = 0;
+  const int rc = sized_ingest<1>(
+      ctx, "wire_mvreg_ops_ingest", N, o, out != nullptr, totals ? &n_ops : nullptr,
+      [&](u64 *counts) {
+        p.counts = counts;
+        hipLaunchKernelGGL(mvops_count_kernel, dim3(grid), dim3(kBlock), ring_bytes, ctx->stream, p);
+      },
+      [&] {
+        p.op_off = op_off;
+        const unsigned long long dw = (p.A + 1) / 2;
+        p.dict_words = dw * 8 + ring_bytes <= kMvLdsMax ? dw : 0;  // else: searched in global memory
+        hipLaunchKernelGGL(mvops_fill_kernel, dim3(grid), dim3(kBlock), ring_bytes + p.dict_words * 8, ctx->stream, p);
+      });
+  if (!rc && totals) totals[0] = totals[1] = n_ops;
+  return rc;
 }
 
 int crdt_mvreg_ops_egress(crdt_ctx *ctx, const crdt_mvreg_ops *ops, size_t N, const uint32_t *actors, size_t A,
@@ -522,23 +474,8 @@ int crdt_mvreg_ops_egress(crdt_ctx *ctx, const crdt_mvreg_ops *ops, size_t N, co
   p.val = (const u64 *)ops->val;
   p.actors = actors;
   p.status = status;
-  CRDT_HIP(ctx, hipSetDevice(ctx->device));
-  u64 *sizes = nullptr;
-  if (int rc = wire_scratch(ctx, N, &sizes)) return rc;
-  p.sizes = sizes;
-  const unsigned grid = wave_grid(ctx, N, kMvWpb, 32);
-  timing_begin(ctx, "wire_mvreg_ops_egress");
-  hipLaunchKernelGGL(mvops_egress_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, p, 0);
-  int rc = hipGetLastError() == hipSuccess ? CRDT_OK : fail(ctx, CRDT_EHIP, "mvreg_ops_egress: count launch");
-  if (!rc) rc = egress_layout(ctx, sizes, (u64 *)frame_off, N, total);
-  if (!rc && bytes && cap >= *total) {
-    p.frame_off = (const u64 *)frame_off;
-    p.bytes = bytes;
-    hipLaunchKernelGGL(mvops_egress_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, p, 1);
-    if (hipGetLastError() != hipSuccess) rc = fail(ctx, CRDT_EHIP, "mvreg_ops_egress: write launch");
-  }
-  timing_end(ctx);
-  return rc;
+  return two_pass_egress(ctx, "wire_mvreg_ops_egress", mvops_egress_kernel, p, wave_grid(ctx, N, kMvWpb, 32), frame_off, bytes,
+                         cap, total);
 }
 
 }  // extern "C"

@@ -14,13 +14,13 @@
 // The dense `kind` arrays keep their meaning (Orswot 0 = Add, Map 0 = Up): the Map tag is flipped on
 // the way in and out.
 //
-// Ingest is count -> three exclusive scans -> finalize (capacities) -> fill, one wave per frame in
-// both passes.  A frame is one dependent chain (an op's length decides where the next begins): the
+// Ingest is count -> three exclusive scans -> finalize (capacities) -> fill (the sized ingest of
+// wire_driver.hpp), one wave per frame in both passes.  A frame is one dependent chain (an op's length decides where the next begins): the
 // walk reads only tags and counts, through the LDS-ring reader of wire_common.hpp; every 64 ops
 // found the parse runs with lane = op (dot / clock records, dictionary lookups, stores straight
 // into the op's SoA slots and its zeroed clock row).  The count pass settles malformed frames and,
 // through finalize, capacities, so the fill pass writes only whole, valid states.
-// Egress is count (lane = op) -> wave prefix sum -> scan over states -> write.
+// Egress is count (lane = op) -> wave prefix sum -> scan over states -> write (wire_driver.hpp's two passes).
 #include "wire_ops_common.hpp"
 
 namespace crdt {
@@ -146,34 +146,6 @@ __global__ __launch_bounds__(kBlock) void ops_count_kernel(OpsPlan p) {
       p.counts[2 * p.N + s] = ni;
     }
   }
-}
-
-// raw [3][N+1]: the scans of the counts.  The first state whose ops, rows or ids end past a capacity
-// and every state after it get bit 2 and no room: their offsets repeat that state's start.
-__global__ __launch_bounds__(kBlock) void ops_finalize_kernel(const u64 *raw, unsigned long long N, u64 cap_op, u64 cap_row,
-                                                              u64 cap_id, u64 *op_off, u64 *row_off, u64 *id_off,
-                                                              uint32_t *status, u64 *ids_off) {
-  const unsigned long long i = blockIdx.x * (unsigned long long)kBlock + threadIdx.x;
-  if (i > N) return;
-  auto first_over = [&](const u64 *r, u64 cap) {  // r ascends
-    unsigned long long lo = 0, hi = N;
-    while (lo < hi) {
-      const unsigned long long mid = (lo + hi) / 2;
-      if (r[mid + 1] > cap) hi = mid;
-      else lo = mid + 1;
-    }
-    return lo;
-  };
-  unsigned long long c = first_over(raw, cap_op);
-  const unsigned long long c1 = first_over(raw + (N + 1), cap_row), c2 = first_over(raw + 2 * (N + 1), cap_id);
-  c = c1 < c ? c1 : c;
-  c = c2 < c ? c2 : c;
-  const unsigned long long j = i < c ? i : c;
-  op_off[i] = raw[j];
-  row_off[i] = raw[(N + 1) + j];
-  id_off[i] = raw[2 * (N + 1) + j];
-  if (i < N && i >= c) status[i] |= kWireCap;
-  if (i == 0 && ids_off) ids_off[0] = 0;
 }
 
 // One op's id list: u64 member ids (Orswot) or u32 key ids (Map) at word `pos` -> dictionary indices.
@@ -499,83 +471,32 @@ __global__ __launch_bounds__(kBlock) void ops_egress_kernel(OpsEgressPlan p, int
 }
 
 // ---- host -----------------------------------------------------------------------------------------
-// The launches of one ingest, between the caller's timing_begin / timing_end (an error return
-// passes through timing_end too, so no timing entry is left without its stop event).
-template <bool MAP>
-static int ops_ingest_launch(crdt_ctx *ctx, OpsPlan &p, u64 *raw, u64 *sc, u64 cap_op, u64 cap_row, u64 cap_id,
-                             bool fill, u64 *op_off, u64 *row_off, u64 *id_off) {
-  const unsigned long long N = p.N;
-  const size_t ring_bytes = (size_t)kOpsWpb * kWalkRing * kWalkWin * 4;
-  const unsigned grid = wave_grid(ctx, N, kOpsWpb, 8);
-  hipLaunchKernelGGL(ops_count_kernel<MAP>, dim3(grid), dim3(kBlock), ring_bytes, ctx->stream, p);
-  CRDT_HIP(ctx, hipGetLastError());
-  for (int j = 0; j < 3; ++j)
-    if (int rc = exclusive_scan(ctx, p.counts + j * N, raw + j * (N + 1), N, sc, nullptr)) return rc;
-  if (!fill) return CRDT_OK;
-  hipLaunchKernelGGL(ops_finalize_kernel, dim3((unsigned)((N + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream,
-                     (const u64 *)raw, N, cap_op, cap_row, cap_id, op_off, row_off, id_off, p.status, p.ids_off);
-  CRDT_HIP(ctx, hipGetLastError());
-  p.op_off = op_off;
-  p.row_off = row_off;
-  p.id_off = id_off;
-  const unsigned long long dw = (p.A + 1) / 2 + (MAP ? (p.U + 1) / 2 : p.U);
-  p.dict_words = dw * 8 + ring_bytes <= kOpsLdsMax ? dw : 0;  // else: searched in global memory
-  hipLaunchKernelGGL(ops_fill_kernel<MAP>, dim3(grid), dim3(kBlock), ring_bytes + p.dict_words * 8, ctx->stream, p);
-  CRDT_HIP(ctx, hipGetLastError());
-  return CRDT_OK;
-}
-
 template <bool MAP>
 static int ops_ingest(crdt_ctx *ctx, OpsPlan p, u64 cap_op, u64 cap_row, u64 cap_id, bool fill, u64 *op_off,
                       u64 *row_off, u64 *id_off, uint64_t *totals, const char *what) {
-  const unsigned long long N = p.N;
-  CRDT_HIP(ctx, hipSetDevice(ctx->device));
-  // scratch: counts [3][N] | raw offsets [3][N+1] | scan scratch
-  const unsigned long long nb = (N + kScanItems - 1) / kScanItems + 2;
-  if (int rc = ensure_scratch(ctx, (3 * N + 3 * (N + 1) + nb + 8) * 8)) return rc;
-  u64 *counts = reinterpret_cast<u64 *>(ctx->scratch), *raw = counts + 3 * N, *sc = raw + 3 * (N + 1);
-  p.counts = counts;
-  timing_begin(ctx, what);
-  const int rc = ops_ingest_launch<MAP>(ctx, p, raw, sc, cap_op, cap_row, cap_id, fill, op_off, row_off, id_off);
-  timing_end(ctx);
-  if (rc) return rc;
-  if (totals) {
-    u64 t[3] = {0, 0, 0};
-    for (int j = 0; j < 3; ++j)
-      CRDT_HIP(ctx, hipMemcpyAsync(&t[j], raw + j * (N + 1) + N, 8, hipMemcpyDeviceToHost, ctx->stream));
-    CRDT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int j = 0; j < 3; ++j) totals[j] = t[j];
-  }
-  return CRDT_OK;
-}
-
-template <bool MAP>
-static int ops_egress_launch(crdt_ctx *ctx, OpsEgressPlan &p, uint64_t *frame_off, uint8_t *bytes, size_t cap,
-                             size_t *total) {
-  const unsigned grid = wave_grid(ctx, p.N, kOpsWpb, 32);
-  hipLaunchKernelGGL(ops_egress_kernel<MAP>, dim3(grid), dim3(kBlock), 0, ctx->stream, p, 0);
-  CRDT_HIP(ctx, hipGetLastError());
-  if (int rc = egress_layout(ctx, p.sizes, (u64 *)frame_off, p.N, total)) return rc;
-  if (bytes && cap >= *total) {
-    p.frame_off = (const u64 *)frame_off;
-    p.bytes = bytes;
-    hipLaunchKernelGGL(ops_egress_kernel<MAP>, dim3(grid), dim3(kBlock), 0, ctx->stream, p, 1);
-    CRDT_HIP(ctx, hipGetLastError());
-  }
-  return CRDT_OK;
+  const size_t ring_bytes = (size_t)kOpsWpb * kWalkRing * kWalkWin * 4;
+  const unsigned grid = wave_grid(ctx, p.N, kOpsWpb, 8);
+  const SizedOut<3> o{{cap_op, cap_row, cap_id}, {op_off, row_off, id_off}, {p.ids_off, nullptr}, p.status};
+  return sized_ingest<3>(
+      ctx, what, p.N, o, fill, totals,
+      [&](u64 *counts) {
+        p.counts = counts;
+        hipLaunchKernelGGL(ops_count_kernel<MAP>, dim3(grid), dim3(kBlock), ring_bytes, ctx->stream, p);
+      },
+      [&] {
+        p.op_off = op_off;
+        p.row_off = row_off;
+        p.id_off = id_off;
+        const unsigned long long dw = (p.A + 1) / 2 + (MAP ? (p.U + 1) / 2 : p.U);
+        p.dict_words = dw * 8 + ring_bytes <= kOpsLdsMax ? dw : 0;  // else: searched in global memory
+        hipLaunchKernelGGL(ops_fill_kernel<MAP>, dim3(grid), dim3(kBlock), ring_bytes + p.dict_words * 8, ctx->stream, p);
+      });
 }
 
 template <bool MAP>
 static int ops_egress(crdt_ctx *ctx, OpsEgressPlan p, uint64_t *frame_off, uint8_t *bytes, size_t cap, size_t *total,
                       const char *what) {
-  CRDT_HIP(ctx, hipSetDevice(ctx->device));
-  u64 *sizes = nullptr;
-  if (int rc = wire_scratch(ctx, p.N, &sizes)) return rc;
-  p.sizes = sizes;
-  timing_begin(ctx, what);
-  const int rc = ops_egress_launch<MAP>(ctx, p, frame_off, bytes, cap, total);
-  timing_end(ctx);
-  return rc;
+  return two_pass_egress(ctx, what, ops_egress_kernel<MAP>, p, wave_grid(ctx, p.N, kOpsWpb, 32), frame_off, bytes, cap, total);
 }
 
 }  // namespace crdt

@@ -2,7 +2,7 @@
 // the value-typed Maps' ops; wire_mvreg.hip: the standalone MVReg's Puts): the frame walk's reader and
 // the wave prefix sum of the egress.
 #pragma once
-#include "wire_common.hpp"
+#include "wire_driver.hpp"
 
 namespace crdt {
 

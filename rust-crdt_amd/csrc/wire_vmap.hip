@@ -21,7 +21,7 @@
 // unspecified in the reference: any order decodes to the same state).
 // A key is present iff its entry clock row is nonzero, a member iff its dot row is (the fold
 // layouts' convention); a nested Orswot's deferred removes are slots 0 .. vd_n of its key.
-#include "wire_common.hpp"
+#include "wire_driver.hpp"
 
 namespace crdt {
 
@@ -626,23 +626,8 @@ static int vmap_egress(crdt_ctx *ctx, VMapWirePlan &p, uint64_t *frame_off, uint
   const size_t N = p.N;
   if (N == 0) return CRDT_OK;
   if (!frame_off || !total) return fail(ctx, CRDT_EINVAL, "%s: need frame_off and total", what);
-  CRDT_HIP(ctx, hipSetDevice(ctx->device));
-  u64 *sizes = nullptr;
-  if (int rc = wire_scratch(ctx, N, &sizes)) return rc;
-  p.sizes = sizes;
-  const unsigned grid = wave_grid(ctx, N, 4, 32);
-  timing_begin(ctx, "wire_egress");
-  hipLaunchKernelGGL(vmap_egress_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, p, 0);
-  CRDT_HIP(ctx, hipGetLastError());
-  if (int rc = egress_layout(ctx, sizes, (u64 *)frame_off, N, total)) return rc;
-  if (bytes && cap >= *total) {
-    p.frame_out = (const u64 *)frame_off;
-    p.out = bytes;
-    hipLaunchKernelGGL(vmap_egress_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, p, 1);
-    CRDT_HIP(ctx, hipGetLastError());
-  }
-  timing_end(ctx);
-  return CRDT_OK;
+  return two_pass_egress(ctx, "wire_egress", vmap_egress_kernel, p, wave_grid(ctx, N, 4, 32), frame_off, bytes, cap, total,
+                         StatePlanOut{});
 }
 
 }  // namespace crdt

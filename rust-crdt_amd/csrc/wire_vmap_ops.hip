@@ -256,36 +256,6 @@ struct VoCaps {
   u64 c[4];
 };
 
-// raw [4][N+1]: the scans of the counts.  The first state whose ops, rows, keys or members end past
-// a capacity and every state after it get bit 2 and no room: their offsets repeat that state's start.
-__global__ __launch_bounds__(kBlock) void vops_finalize_kernel(const u64 *raw, unsigned long long N, VoCaps caps, u64 *op_off,
-                                                               u64 *row_off, u64 *key_first, u64 *mem_first,
-                                                               uint32_t *status, u64 *key_off, u64 *mem_off) {
-  const unsigned long long i = blockIdx.x * (unsigned long long)kBlock + threadIdx.x;
-  if (i > N) return;
-  unsigned long long c = N;
-  for (int j = 0; j < 4; ++j) {  // every raw[j] ascends
-    const u64 *r = raw + j * (N + 1);
-    unsigned long long lo = 0, hi = N;
-    while (lo < hi) {
-      const unsigned long long mid = (lo + hi) / 2;
-      if (r[mid + 1] > caps.c[j]) hi = mid;
-      else lo = mid + 1;
-    }
-    c = lo < c ? lo : c;
-  }
-  const unsigned long long j = i < c ? i : c;
-  op_off[i] = raw[j];
-  row_off[i] = raw[(N + 1) + j];
-  key_first[i] = raw[2 * (N + 1) + j];
-  mem_first[i] = raw[3 * (N + 1) + j];
-  if (i < N && i >= c) status[i] |= kWireCap;
-  if (i == 0) {
-    if (key_off) key_off[0] = 0;
-    if (mem_off) mem_off[0] = 0;
-  }
-}
-
 template <int V>
 __global__ __launch_bounds__(kBlock) void vops_fill_kernel(VOpsPlan p) {
   extern __shared__ u64 lds[];
@@ -317,7 +287,8 @@ __global__ __launch_bounds__(kBlock) void vops_fill_kernel(VOpsPlan p) {
   for (unsigned long long s = (unsigned long long)blockIdx.x * kVoWpb + wib; s < p.N;
        s += (unsigned long long)gridDim.x * kVoWpb) {
     const unsigned st = p.status[s];
-    const u64 o0 = p.op_off[s], r0 = p.row_off[s], k0 = p.key_first[s], m0 = p.mem_first[s];
+    const u64 o0 = p.op_off[s], r0 = p.row_off[s], k0 = p.key_first[s];
+    const u64 m0 = V == kVOrswot ? p.mem_first[s] : 0;  // (the other Maps have no members and no mem_first)
     OpWalk w;
     if ((st & (kWireBad | kWireCap)) || p.op_off[s + 1] == o0 || !vops_frame(p, s, w, ring)) continue;
     w.start(lane);
@@ -768,101 +739,49 @@ __global__ __launch_bounds__(kBlock) void vops_egress_kernel(VOpsEgressPlan p, i
 }
 
 // ---- host -----------------------------------------------------------------------------------------
-// The launches of one ingest, between the caller's timing_begin / timing_end (an error return
-// passes through timing_end too, so no timing entry is left without its stop event).
-template <int V>
-static int vops_ingest_launch(crdt_ctx *ctx, VOpsPlan &p, u64 *raw, u64 *sc, const VoCaps &caps, bool fill, u64 *op_off,
-                              u64 *row_off, u64 *key_first, u64 *mem_first) {
-  const unsigned long long N = p.N;
-  const size_t ring_bytes = (size_t)kVoWpb * kWalkRing * kWalkWin * 4;
-  const unsigned grid = wave_grid(ctx, N, kVoWpb, 8);
-  hipLaunchKernelGGL(vops_count_kernel<V>, dim3(grid), dim3(kBlock), ring_bytes, ctx->stream, p);
-  CRDT_HIP(ctx, hipGetLastError());
-  for (int j = 0; j < 4; ++j)
-    if (int rc = exclusive_scan(ctx, p.counts + j * N, raw + j * (N + 1), N, sc, nullptr)) return rc;
-  if (!fill) return CRDT_OK;
-  hipLaunchKernelGGL(vops_finalize_kernel, dim3((unsigned)((N + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream,
-                     (const u64 *)raw, N, caps, op_off, row_off, key_first, mem_first, p.status, p.key_off, p.mem_off);
-  CRDT_HIP(ctx, hipGetLastError());
-  p.op_off = op_off;
-  p.row_off = row_off;
-  p.key_first = key_first;
-  p.mem_first = mem_first;
-  const unsigned long long dw =
-      (p.A + 1) / 2 + (p.K + 1) / 2 + (V == kVOrswot ? p.U : (V == kVNested ? (p.U + 1) / 2 : 0));
-  p.dict_words = dw * 8 + ring_bytes <= kVoLdsMax ? dw : 0;  // else: searched in global memory
-  hipLaunchKernelGGL(vops_fill_kernel<V>, dim3(grid), dim3(kBlock), ring_bytes + p.dict_words * 8, ctx->stream, p);
-  CRDT_HIP(ctx, hipGetLastError());
-  return CRDT_OK;
-}
-
 template <int V>
 static int vops_ingest(crdt_ctx *ctx, VOpsPlan p, const VoCaps &caps, bool fill, u64 *op_off, u64 *row_off, u64 *key_first,
-                       u64 *mem_first, uint64_t *totals, const char *what) {
-  const unsigned long long N = p.N;
-  CRDT_HIP(ctx, hipSetDevice(ctx->device));
-  // scratch: counts [4][N] | raw offsets [4][N+1] | member offsets of a Map without members [N+1] | scan scratch
-  const unsigned long long nb = (N + kScanItems - 1) / kScanItems + 2;
-  if (int rc = ensure_scratch(ctx, (4 * N + 5 * (N + 1) + nb + 8) * 8)) return rc;
-  u64 *counts = reinterpret_cast<u64 *>(ctx->scratch), *raw = counts + 4 * N, *mtmp = raw + 4 * (N + 1), *sc = mtmp + (N + 1);
-  p.counts = counts;
-  timing_begin(ctx, what);
-  const int rc = vops_ingest_launch<V>(ctx, p, raw, sc, caps, fill, op_off, row_off, key_first, mem_first ? mem_first : mtmp);
-  timing_end(ctx);
-  if (rc) return rc;
-  if (totals) {
-    u64 t[4] = {0, 0, 0, 0};
-    for (int j = 0; j < 4; ++j)
-      CRDT_HIP(ctx, hipMemcpyAsync(&t[j], raw + j * (N + 1) + N, 8, hipMemcpyDeviceToHost, ctx->stream));
-    CRDT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int j = 0; j < 4; ++j) totals[j] = t[j];
-  }
-  return CRDT_OK;
+                       u64 *mem_first, uint64_t *totals) {
+  const size_t ring_bytes = (size_t)kVoWpb * kWalkRing * kWalkWin * 4;
+  const unsigned grid = wave_grid(ctx, p.N, kVoWpb, 8);
+  // (a Map without members passes no mem_first: its member count is always 0 and is not read back)
+  const SizedOut<4> o{{caps.c[0], caps.c[1], caps.c[2], caps.c[3]}, {op_off, row_off, key_first, mem_first},
+                      {p.key_off, p.mem_off}, p.status};
+  return sized_ingest<4>(
+      ctx, "wire_vmap_ops_ingest", p.N, o, fill, totals,
+      [&](u64 *counts) {
+        p.counts = counts;
+        hipLaunchKernelGGL(vops_count_kernel<V>, dim3(grid), dim3(kBlock), ring_bytes, ctx->stream, p);
+      },
+      [&] {
+        p.op_off = op_off;
+        p.row_off = row_off;
+        p.key_first = key_first;
+        p.mem_first = mem_first;
+        const unsigned long long dw =
+            (p.A + 1) / 2 + (p.K + 1) / 2 + (V == kVOrswot ? p.U : (V == kVNested ? (p.U + 1) / 2 : 0));
+        p.dict_words = dw * 8 + ring_bytes <= kVoLdsMax ? dw : 0;  // else: searched in global memory
+        hipLaunchKernelGGL(vops_fill_kernel<V>, dim3(grid), dim3(kBlock), ring_bytes + p.dict_words * 8, ctx->stream, p);
+      });
 }
 
 static int vops_ingest_any(int V, crdt_ctx *ctx, const VOpsPlan &p, const VoCaps &caps, bool fill, u64 *op_off, u64 *row_off,
                            u64 *key_first, u64 *mem_first, uint64_t *totals) {
-  const char *what = "wire_vmap_ops_ingest";
   switch (V) {
-    case kVG: return vops_ingest<kVG>(ctx, p, caps, fill, op_off, row_off, key_first, mem_first, totals, what);
-    case kVPN: return vops_ingest<kVPN>(ctx, p, caps, fill, op_off, row_off, key_first, mem_first, totals, what);
-    case kVOrswot: return vops_ingest<kVOrswot>(ctx, p, caps, fill, op_off, row_off, key_first, mem_first, totals, what);
-    default: return vops_ingest<kVNested>(ctx, p, caps, fill, op_off, row_off, key_first, mem_first, totals, what);
+    case kVG: return vops_ingest<kVG>(ctx, p, caps, fill, op_off, row_off, key_first, mem_first, totals);
+    case kVPN: return vops_ingest<kVPN>(ctx, p, caps, fill, op_off, row_off, key_first, mem_first, totals);
+    case kVOrswot: return vops_ingest<kVOrswot>(ctx, p, caps, fill, op_off, row_off, key_first, mem_first, totals);
+    default: return vops_ingest<kVNested>(ctx, p, caps, fill, op_off, row_off, key_first, mem_first, totals);
   }
-}
-
-template <int V>
-static int vops_egress_launch(crdt_ctx *ctx, VOpsEgressPlan &p, uint64_t *frame_off, uint8_t *bytes, size_t cap,
-                              size_t *total) {
-  const unsigned grid = wave_grid(ctx, p.N, kVoWpb, 32);
-  hipLaunchKernelGGL(vops_egress_kernel<V>, dim3(grid), dim3(kBlock), 0, ctx->stream, p, 0);
-  CRDT_HIP(ctx, hipGetLastError());
-  if (int rc = egress_layout(ctx, p.sizes, (u64 *)frame_off, p.N, total)) return rc;
-  if (bytes && cap >= *total) {
-    p.frame_off = (const u64 *)frame_off;
-    p.bytes = bytes;
-    hipLaunchKernelGGL(vops_egress_kernel<V>, dim3(grid), dim3(kBlock), 0, ctx->stream, p, 1);
-    CRDT_HIP(ctx, hipGetLastError());
-  }
-  return CRDT_OK;
 }
 
 static int vops_egress(int V, crdt_ctx *ctx, VOpsEgressPlan p, uint64_t *frame_off, uint8_t *bytes, size_t cap,
                        size_t *total) {
-  CRDT_HIP(ctx, hipSetDevice(ctx->device));
-  u64 *sizes = nullptr;
-  if (int rc = wire_scratch(ctx, p.N, &sizes)) return rc;
-  p.sizes = sizes;
-  timing_begin(ctx, "wire_vmap_ops_egress");
-  int rc;
-  switch (V) {
-    case kVG: rc = vops_egress_launch<kVG>(ctx, p, frame_off, bytes, cap, total); break;
-    case kVPN: rc = vops_egress_launch<kVPN>(ctx, p, frame_off, bytes, cap, total); break;
-    case kVOrswot: rc = vops_egress_launch<kVOrswot>(ctx, p, frame_off, bytes, cap, total); break;
-    default: rc = vops_egress_launch<kVNested>(ctx, p, frame_off, bytes, cap, total); break;
-  }
-  timing_end(ctx);
-  return rc;
+  void (*kern)(VOpsEgressPlan, int) = V == kVG       ? vops_egress_kernel<kVG>
+                                      : V == kVPN    ? vops_egress_kernel<kVPN>
+                                      : V == kVOrswot ? vops_egress_kernel<kVOrswot>
+                                                      : vops_egress_kernel<kVNested>;
+  return two_pass_egress(ctx, "wire_vmap_ops_egress", kern, p, wave_grid(ctx, p.N, kVoWpb, 32), frame_off, bytes, cap, total);
 }
 
 // the argument checks the three ingests share; the plan's dictionaries and frames
