@@ -1130,6 +1130,48 @@ int crdt_orswot_eq_batch(crdt_ctx *ctx, const crdt_orswot_states *x, const crdt_
 int crdt_map_eq_batch(crdt_ctx *ctx, const crdt_map_states *x, const crdt_map_deferred *xd, const crdt_map_states *y,
                       const crdt_map_deferred *yd, uint32_t *ne);
 
+/* The same for the value-typed Maps, on the layouts of their merge_batch (crdt_map_counter_states /
+ * crdt_map_orswot_states / crdt_map_nested_states + crdt_map_deferred; a NULL crdt_map_deferred means
+ * no Map-level slots).  Map's PartialEq is derived for any V (map.rs:31-47), so ne[i] is 0 iff
+ * x[i] == y[i] with the value type's own PartialEq per key, else the complete set of:
+ *  - CRDT_NE_CLOCK: the Map's clock row differs.
+ *  - CRDT_NE_ENTRIES: some key's entry clock ec[s][k] differs, word by word.  A key is absent exactly
+ *    when that row is all zero.
+ *  - CRDT_NE_VALUES: for some key the values differ.  The value of a key absent on a side is
+ *    V::default(), whatever that key's value arrays hold (the rule crdt_map_eq_batch states for
+ *    registers): a key present on one side only differs in its value iff the present value is not
+ *    the default one.
+ *      Counters (gcounter.rs, pncounter.rs: derived over the inner VClocks): the W rows
+ *        val[s][k][w][.], word by word over the full u64.
+ *      Orswot (orswot.rs:20, derived): oc[s][k]; the member rows ent[s][k][m][.] (an absent member is
+ *        an all-zero row); the first vd_n[s][k] nested deferred slots as a map rm clock -> member set
+ *        with the rules of the Map-level list below.  Slots at or past vd_n are never read; Vd may
+ *        differ between the sides.
+ *      Inner Map (map.rs:31-47 one level down): ic[s][k]; iec[s][k][j] (an inner key is absent iff
+ *        that row is all zero, and its register is then the empty one); the first id_n[s][k] inner
+ *        deferred slots as a map rm clock -> inner-key set; each present inner key's register as a
+ *        set of (clock row, value) over the non-empty slots among its first nval[s][k][j] slots, the
+ *        order-free rule of mvreg.rs:62-86 (the value is compared, a pair held twice counts once, Vs
+ *        may differ between the sides).  Rows past nval / id_n are never read.
+ *  - CRDT_NE_DEFERRED: the Map-level deferred removes differ as a map rm clock -> key set, exactly as
+ *    in crdt_map_eq_batch (slot order and Dcap irrelevant, equal clocks within one side union their
+ *    sets, {c: {}} != {}).
+ *  - CRDT_NE_INVALID, alone, when on either side def_count > Dcap, some vd_n[s][k] > Vd, some
+ *    id_n[s][k] > Id or some nval[s][k][j] > Vs (of any key, present or not).  Neighbouring pairs are
+ *    unaffected.
+ * Limits (past them CRDT_EUNSUPPORTED before any launch): counters A <= 1,024, W in {1, 2}; Orswot
+ * values A <= 1,024, M <= 1,024; nested A <= 256, K2 <= 256, Vs <= 64.  Vd, Id and Dcap are not
+ * bounded: the result is exact for any number of live slots.  N, K, A and W / M / K2 must match
+ * across the sides (CRDT_EINVAL).  N == 0 returns CRDT_OK.  x and y may alias (every word is then 0).
+ * Both sides are read only; the calls allocate nothing and do not synchronise with the host.  Device
+ * memory only. */
+int crdt_map_counter_eq_batch(crdt_ctx *ctx, const crdt_map_counter_states *x, const crdt_map_deferred *xd,
+                              const crdt_map_counter_states *y, const crdt_map_deferred *yd, uint32_t *ne);
+int crdt_map_orswot_eq_batch(crdt_ctx *ctx, const crdt_map_orswot_states *x, const crdt_map_deferred *xd,
+                             const crdt_map_orswot_states *y, const crdt_map_deferred *yd, uint32_t *ne);
+int crdt_map_nested_eq_batch(crdt_ctx *ctx, const crdt_map_nested_states *x, const crdt_map_deferred *xd,
+                             const crdt_map_nested_states *y, const crdt_map_deferred *yd, uint32_t *ne);
+
 /* ---- causal helpers on dense clock rows -----------------------------------
  * Row-pair ops over N pairs (x_i, y_i) of A-word rows (VClock, GCounter inner, or a PNCounter
  * P‖N row with A = 2·actors):

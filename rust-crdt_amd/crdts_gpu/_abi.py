@@ -76,6 +76,7 @@ EXPORTS = (
     "crdt_vclock_ops_ingest", "crdt_pncounter_ops_ingest", "crdt_gset_ops_ingest", "crdt_lwwreg_ops_ingest",
     "crdt_vclock_ops_egress", "crdt_pncounter_ops_egress", "crdt_gset_ops_egress", "crdt_lwwreg_ops_egress",
     "crdt_mvreg_eq_batch", "crdt_orswot_eq_batch", "crdt_map_eq_batch",
+    "crdt_map_counter_eq_batch", "crdt_map_orswot_eq_batch", "crdt_map_nested_eq_batch",
 )
 
 
@@ -490,6 +491,11 @@ _SIGS.update({  # batched state equality (csrc/eq.hip)
     "crdt_orswot_eq_batch": ([P, ctypes.POINTER(OrswotStates), ctypes.POINTER(OrswotStates), P], ctypes.c_int),
     "crdt_map_eq_batch": ([P, ctypes.POINTER(MapStates), ctypes.POINTER(MapDeferred), ctypes.POINTER(MapStates),
                            ctypes.POINTER(MapDeferred), P], ctypes.c_int),
+})
+_SIGS.update({  # ... of the value-typed Maps (csrc/eq_vmap.hip)
+    f"crdt_map_{_n}_eq_batch": ([P, ctypes.POINTER(_st), ctypes.POINTER(MapDeferred), ctypes.POINTER(_st),
+                                 ctypes.POINTER(MapDeferred), P], ctypes.c_int)
+    for _n, _st in (("counter", MapCounterStates), ("orswot", MapOrswotStates), ("nested", MapNestedStates))
 })
 for _t in ("vclock", "pncounter", "gset"):
     _SIGS[f"crdt_{_t}_ops_ingest"] = ([P, P, P, S, P, S, ctypes.POINTER(DotOpsBuf), P, ctypes.POINTER(U64)], ctypes.c_int)

@@ -1390,6 +1390,110 @@ def nested_merge_batch(me, other, ctx: Optional[Context] = None) -> torch.Tensor
     return _vm_call(ctx, "crdt_map_nested_merge_batch", sa, sb, me, other, N, A, K, what)
 
 
+# ---- Batched state equality of value-typed Map states (csrc/eq_vmap.hip) ---------------------------
+# x[i] == y[i] by Map's derived PartialEq (map.rs:31-47) with the value type's own PartialEq per key, on
+# the objects the matching *_merge_batch takes.  Unlike merge_batch the sides may differ in Vd / Id /
+# Vs / Dcap; every other dimension must match.  Both sides are read only.  Returns ne (N,) int32: 0 =
+# equal, else the OR of NE_CLOCK / NE_ENTRIES / NE_VALUES / NE_DEFERRED for every component that
+# differs, or NE_INVALID alone when a def_count, vd_n, id_n or nval is above its capacity.
+def _veq_fields(x, y, fields, what):
+    for nm in fields:
+        a, b = getattr(x, nm), getattr(y, nm)
+        if a.device != b.device or a.device != x.clock.device:
+            raise ValueError(f"{what}: x.{nm} and y.{nm} must be on the states' device")
+        if not a.is_contiguous() or not b.is_contiguous():
+            raise ValueError(f"{what}: {nm} must be contiguous")
+
+
+def _veq_call(ctx, fn, sa, sb, x, y, N, A, K, what):
+    Kw = (K + 63) // 64
+    da, db = _vm_deferred(ctx, x, N, A, Kw, f"{what}(x)"), _vm_deferred(ctx, y, N, A, Kw, f"{what}(y)")
+    ne = torch.empty(N, dtype=torch.int32, device=x.clock.device)
+    ctx.call(fn, ctypes.byref(sa), ctypes.byref(da), ctypes.byref(sb), ctypes.byref(db), ne.data_ptr())
+    return ne
+
+
+def counter_eq_batch(x, y, ctx: Optional[Context] = None) -> torch.Tensor:
+    """x[i] == y[i] for N pairs of Map<K, GCounter / PNCounter> states (crdt_map_counter_eq_batch):
+    clock (N, A), ec (N, K, A), val (N, K, W, A), def_clock (N, Dcap, A), def_keys (N, Dcap, Kw),
+    def_count (N,) int32; Dcap may differ between the sides.  Returns ne (N,) int32."""
+    what = "map.counter_eq_batch"
+    _same_shapes(x, y, ("clock", "ec", "val"), what)
+    ctx = ctx or Context.default(x.clock.device.index)
+    if x.clock.dim() != 2 or x.ec.dim() != 3 or x.val.dim() != 4:
+        raise ValueError(f"{what}: clock (N, A), ec (N, K, A), val (N, K, W, A) expected")
+    N, A = x.clock.shape
+    K, W = x.ec.shape[1], x.val.shape[2]
+    if tuple(x.ec.shape) != (N, K, A) or tuple(x.val.shape) != (N, K, W, A):
+        raise ValueError(f"{what}: clock (N, A), ec (N, K, A), val (N, K, W, A) expected")
+    if N == 0:
+        return torch.zeros(0, dtype=torch.int32, device=x.clock.device)
+    sts = []
+    for st in (x, y):
+        for t, nm in ((st.clock, "clock"), (st.ec, "ec"), (st.val, "val")):
+            ctx.check_tensor(t, f"{what}({nm})")
+        s = _abi.MapCounterStates()
+        s.N, s.K, s.A, s.W = N, K, A, W
+        s.clock, s.clock_stride = st.clock.data_ptr(), A
+        s.ec, s.ec_stride = st.ec.data_ptr(), K * A
+        s.val, s.val_stride = st.val.data_ptr(), K * W * A
+        sts.append(s)
+    return _veq_call(ctx, "crdt_map_counter_eq_batch", sts[0], sts[1], x, y, N, A, K, what)
+
+
+def orswot_eq_batch(x, y, ctx: Optional[Context] = None) -> torch.Tensor:
+    """x[i] == y[i] for N pairs of Map<K, Orswot<M>> states (crdt_map_orswot_eq_batch): the
+    crdt_map_orswot_states layout (clock, ec, oc, ent, vd_n, vd_clock, vd_mem) + the Map's deferred slots
+    def_clock / def_keys / def_count; Vd and Dcap may differ between the sides.  Returns ne (N,) int32."""
+    what = "map.orswot_eq_batch"
+    _same_shapes(x, y, ("clock", "ec", "oc", "ent", "vd_n"), what)
+    _veq_fields(x, y, ("vd_clock", "vd_mem"), what)
+    ctx = ctx or Context.default(x.clock.device.index)
+    if x.clock.dim() != 2 or x.ent.dim() != 4:
+        raise ValueError(f"{what}: clock (N, A) and ent (N, K, M, A) expected")
+    N, A = x.clock.shape
+    K, M = x.ent.shape[1], x.ent.shape[2]
+    if tuple(x.ec.shape) != (N, K, A) or tuple(x.oc.shape) != (N, K, A) or tuple(x.ent.shape) != (N, K, M, A):
+        raise ValueError(f"{what}: ec / oc (N, K, A) and ent (N, K, M, A) expected")
+    if N == 0:
+        return torch.zeros(0, dtype=torch.int32, device=x.clock.device)
+    sts = []
+    for st in (x, y):
+        for nm in ("clock", "ec", "oc", "ent", "vd_clock", "vd_mem"):
+            ctx.check_tensor(getattr(st, nm), f"{what}({nm})")
+        if st.vd_n.dtype != torch.int32 or tuple(st.vd_n.shape) != (N, K):
+            raise ValueError(f"{what}: vd_n must be an (N, K) int32 tensor")
+        s = _abi.MapOrswotStates()
+        s.N, s.K, s.M, s.A = N, K, M, A
+        s.Vd = _vd_slots(st, N, K, M, A, what)
+        s.clock, s.ec, s.oc, s.ent = st.clock.data_ptr(), st.ec.data_ptr(), st.oc.data_ptr(), st.ent.data_ptr()
+        s.vd_n, s.vd_clock, s.vd_mem = st.vd_n.data_ptr(), st.vd_clock.data_ptr(), st.vd_mem.data_ptr()
+        sts.append(s)
+    return _veq_call(ctx, "crdt_map_orswot_eq_batch", sts[0], sts[1], x, y, N, A, K, what)
+
+
+def nested_eq_batch(x, y, ctx: Optional[Context] = None) -> torch.Tensor:
+    """x[i] == y[i] for N pairs of Map<K, Map<K2, MVReg<u64>>> states (crdt_map_nested_eq_batch): the
+    crdt_map_nested_states layout (clock, ec, ic, iec, ivc, ivv, nval, id_n, id_clock, id_keys) + the outer
+    deferred slots def_clock / def_keys / def_count; Id, Vs and Dcap may differ between the sides.  Returns
+    ne (N,) int32."""
+    what = "map.nested_eq_batch"
+    _same_shapes(x, y, ("clock", "ec", "ic", "iec", "nval", "id_n"), what)
+    _veq_fields(x, y, ("ivc", "ivv", "id_clock", "id_keys"), what)
+    ctx = ctx or Context.default(x.clock.device.index)
+    if x.clock.dim() == 2 and x.clock.shape[0] == 0:
+        return torch.zeros(0, dtype=torch.int32, device=x.clock.device)
+    sa, N, K, A = _nested_states(x, f"{what}(x)")
+    sb, _, _, _ = _nested_states(y, f"{what}(y)")
+    for st in (x, y):
+        for nm in ("clock", "ec", "ic", "iec", "ivc", "ivv", "id_clock", "id_keys"):
+            ctx.check_tensor(getattr(st, nm), f"{what}({nm})")
+        for nm in ("nval", "id_n"):
+            if getattr(st, nm).dtype != torch.int32:
+                raise ValueError(f"{what}: {nm} must be an int32 tensor")
+    return _veq_call(ctx, "crdt_map_nested_eq_batch", sa, sb, x, y, N, A, K, what)
+
+
 # ---------------------------------------------------------------------------------------------
 # Batched reads: Map::is_empty / len / get / read_ctx (map.rs:233-307) as ReadCtx (readctx.py)
 # ---------------------------------------------------------------------------------------------

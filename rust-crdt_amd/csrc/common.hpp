@@ -128,6 +128,8 @@ struct Tune {
                                //     per output word, no loop)
   int read_unroll = 8;         // ... loads per lane in flight before the first is tested (4, 8)
   int read_nt = 1;             // ... non-temporal loads (the entries are read once)
+  int eqv_ppl = 8;             // value-typed Map equality, per-key kernel: 16-byte pieces per lane of a key's segment
+  int eqv_bpc = 32;            // ... workgroups per CU of its grid-stride loop (and of the register kernel's)
 };
 
 struct PendingTiming {

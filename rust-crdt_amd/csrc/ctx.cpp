@@ -266,6 +266,8 @@ static void apply_tune(crdt_ctx *ctx, const char *t) {
       else if (k == "mpbpc" && v >= 1 && v <= 4096) ctx->tune.map_pair_bpc = v;
       else if (k == "mfbpc" && v >= 1 && v <= 64) ctx->tune.map_forget_bpc = v;
       else if (k == "mvfbpc" && v >= 1 && v <= 64) ctx->tune.mvreg_forget_bpc = v;
+      else if (k == "eqvppl" && v >= 1 && v <= 64) ctx->tune.eqv_ppl = v;
+      else if (k == "eqvbpc" && v >= 1 && v <= 4096) ctx->tune.eqv_bpc = v;
     }
     pos = end + 1;
   }

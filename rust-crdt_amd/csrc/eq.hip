@@ -32,30 +32,12 @@
 //                       re-reading them.
 // The Map's register kernels have K owners per state, so a key that differs ORs its bits into ne[s]
 // with an atomic; keys that are equal (the stream's common case) write nothing.
-#include "common.hpp"
+// The loads, the plans of the dense and deferred kernels and the list compare itself
+// (eq_deferred_pair) are in eq_common.hpp, shared with the value-typed Maps' calls (eq_vmap.hip).
+#include "eq_common.hpp"
 
 namespace crdt {
 
-__device__ __forceinline__ u64x2 eq_ld2(const u64 *p) {
-  return __builtin_nontemporal_load(reinterpret_cast<const u64x2 *>(p));
-}
-__device__ __forceinline__ u64 eq_ld1(const u64 *p) { return __builtin_nontemporal_load(p); }
-
-// ---- clock and entry rows --------------------------------------------------------------------------
-struct EqDenseSide {
-  const u64 *clock;
-  unsigned long long cs;
-  const u64 *rows;
-  unsigned long long rs, ss;  // row stride, state stride
-  const uint32_t *cnt;        // def_count or NULL
-  unsigned long long dcap;
-};
-struct EqDensePlan {
-  EqDenseSide x, y;
-  unsigned long long N, A, R, L;  // R rows of L words per state
-  uint32_t *ne;
-  int lg;  // log2 of the lanes per state; 8: one workgroup per state
-};
 
 // x ^ y over words [0, n) of two rows, lane g of G, ORed into d
 template <bool VEC>
@@ -152,58 +134,6 @@ __global__ __launch_bounds__(kBlock) void eq_dense_kernel(EqDensePlan p) {
 }
 
 // ---- deferred removes ------------------------------------------------------------------------------
-struct EqDefSide {
-  const u64 *clock, *sets;
-  const uint32_t *cnt;
-  unsigned long long dcap;
-};
-struct EqDefPlan {
-  EqDefSide x, y;
-  unsigned long long N, A, W;
-  uint32_t *ne;
-};
-constexpr int kDefWin = 128;  // row hashes kept in LDS per side
-constexpr int kDefAcc = 4;    // set words per lane of one union pass (64 * 4 words = 16,384 members / keys)
-
-__device__ __forceinline__ u64 eq_mix64(u64 z) {
-  z ^= z >> 30;
-  z *= 0xbf58476d1ce4e5b9ull;
-  z ^= z >> 27;
-  z *= 0x94d049bb133111ebull;
-  z ^= z >> 31;
-  return z;
-}
-// the whole wave hashes one row; every lane gets the hash
-__device__ __forceinline__ u64 eq_row_hash(const u64 *r, unsigned long long A, int lane) {
-  u64 h = 0;
-  for (unsigned long long a = lane; a < A; a += kWave) h += eq_mix64(r[a] + 0x9e3779b97f4a7c15ull * (a + 1));
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) h += __shfl_xor(h, off, kWave);
-  return h;
-}
-__device__ __forceinline__ bool eq_row_same(const u64 *r, const u64 *q, unsigned long long A, int lane) {
-  u64 d = 0;
-  for (unsigned long long a = lane; a < A; a += kWave) d |= r[a] ^ q[a];
-  return __ballot(d != 0) == 0;
-}
-// f(j) for every slot j < n of a side whose clock row equals r (hash h): wave-uniform
-template <class F>
-__device__ __forceinline__ void eq_for_matches(const u64 *r, u64 h, const u64 *sc, const u64 *sh, unsigned n,
-                                               unsigned long long A, int lane, F &&f) {
-  const unsigned lim = n < (unsigned)kDefWin ? n : (unsigned)kDefWin;
-  for (unsigned base = 0; base < lim; base += kWave) {
-    const unsigned j = base + lane;
-    u64 m = __ballot(j < lim && sh[j < lim ? j : 0] == h);
-    while (m) {
-      const unsigned jj = base + __builtin_ctzll(m);
-      m &= m - 1;
-      if (eq_row_same(r, sc + (unsigned long long)jj * A, A, lane)) f(jj);
-    }
-  }
-  for (unsigned jj = lim; jj < n; ++jj)
-    if (eq_row_same(r, sc + (unsigned long long)jj * A, A, lane)) f(jj);
-}
-
 __global__ __launch_bounds__(kBlock) void eq_deferred_kernel(EqDefPlan p) {
   __shared__ u64 hsh[kBlock / kWave][2][kDefWin];
   const int lane = threadIdx.x % kWave, wid = threadIdx.x / kWave;
@@ -212,72 +142,19 @@ __global__ __launch_bounds__(kBlock) void eq_deferred_kernel(EqDefPlan p) {
   const unsigned long long wave0 = (blockIdx.x * (unsigned long long)kBlock + threadIdx.x) / kWave;
   const unsigned long long nwave = (unsigned long long)gridDim.x * (kBlock / kWave);
   for (unsigned long long s = wave0; s < p.N; s += nwave) {  // wave-uniform
+    if (p.norm) {  // a per-key owner of an earlier launch reported a bad nested count
+      const unsigned w = p.ne[s];
+      if (w & CRDT_NE_INVALID) {
+        if (lane == 0 && w != CRDT_NE_INVALID) p.ne[s] = CRDT_NE_INVALID;
+        continue;
+      }
+    }
     const unsigned long long cx = p.x.cnt ? p.x.cnt[s] : 0, cy = p.y.cnt ? p.y.cnt[s] : 0;
     if (cx > p.x.dcap || cy > p.y.dcap) continue;  // INVALID, written by the dense kernel
     if (cx == 0 && cy == 0) continue;
-    const unsigned nx = (unsigned)cx, ny = (unsigned)cy;
-    const u64 *xc = p.x.clock + s * p.x.dcap * A, *xm = p.x.sets + s * p.x.dcap * W;
-    const u64 *yc = p.y.clock + s * p.y.dcap * A, *ym = p.y.sets + s * p.y.dcap * W;
-    bool ne = nx == 0 || ny == 0;
-    bool done = ne;
-    if (!done && nx == ny) {  // the same slots in the same order
-      u64 d = 0;
-      for (unsigned long long a = lane; a < nx * A; a += kWave) d |= xc[a] ^ yc[a];
-      for (unsigned long long a = lane; a < nx * W; a += kWave) d |= xm[a] ^ ym[a];
-      done = __ballot(d != 0) == 0;
-    }
-    if (!done) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");  // the previous state's reads of hx / hy
-      for (unsigned j = 0; j < nx && j < (unsigned)kDefWin; ++j) {
-        const u64 h = eq_row_hash(xc + (unsigned long long)j * A, A, lane);
-        if (lane == 0) hx[j] = h;
-      }
-      for (unsigned j = 0; j < ny && j < (unsigned)kDefWin; ++j) {
-        const u64 h = eq_row_hash(yc + (unsigned long long)j * A, A, lane);
-        if (lane == 0) hy[j] = h;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-      // every clock of x is a clock of y, and the unions of their sets agree
-      for (unsigned i = 0; i < nx && !ne; ++i) {
-        const u64 *ri = xc + (unsigned long long)i * A;
-        const u64 h = i < (unsigned)kDefWin ? hx[i] : eq_row_hash(ri, A, lane);
-        unsigned long long cb = 0;
-        do {
-          u64 ux[kDefAcc], uy[kDefAcc];
-#pragma unroll
-          for (int q = 0; q < kDefAcc; ++q) ux[q] = uy[q] = 0;
-          bool fy = false;
-          eq_for_matches(ri, h, xc, hx, nx, A, lane, [&](unsigned j) {
-#pragma unroll
-            for (int q = 0; q < kDefAcc; ++q) {
-              const unsigned long long w = cb + (unsigned long long)q * kWave + lane;
-              if (w < W) ux[q] |= xm[(unsigned long long)j * W + w];
-            }
-          });
-          eq_for_matches(ri, h, yc, hy, ny, A, lane, [&](unsigned j) {
-            fy = true;
-#pragma unroll
-            for (int q = 0; q < kDefAcc; ++q) {
-              const unsigned long long w = cb + (unsigned long long)q * kWave + lane;
-              if (w < W) uy[q] |= ym[(unsigned long long)j * W + w];
-            }
-          });
-          u64 d = 0;
-#pragma unroll
-          for (int q = 0; q < kDefAcc; ++q) d |= ux[q] ^ uy[q];
-          if (!fy || __ballot(d != 0) != 0) ne = true;
-          cb += (unsigned long long)kDefAcc * kWave;
-        } while (cb < W && !ne);
-      }
-      // every clock of y is a clock of x
-      for (unsigned j = 0; j < ny && !ne; ++j) {
-        const u64 *rj = yc + (unsigned long long)j * A;
-        const u64 h = j < (unsigned)kDefWin ? hy[j] : eq_row_hash(rj, A, lane);
-        bool fx = false;
-        eq_for_matches(rj, h, xc, hx, nx, A, lane, [&](unsigned) { fx = true; });
-        if (!fx) ne = true;
-      }
-    }
+    const bool ne = eq_deferred_pair(p.x.clock + s * p.x.dcap * A, p.x.sets + s * p.x.dcap * W, (unsigned)cx,
+                                     p.y.clock + s * p.y.dcap * A, p.y.sets + s * p.y.dcap * W, (unsigned)cy, A, W, lane, hx,
+                                     hy);
     if (ne && lane == 0) p.ne[s] |= CRDT_NE_DEFERRED;
   }
 }
@@ -517,7 +394,7 @@ __global__ __launch_bounds__(1024) void eq_reg_wide_kernel(EqRegPlan p) {
 // ---- launches --------------------------------------------------------------------------------------
 static bool eq_al16(const void *p) { return (uintptr_t)p % 16 == 0; }
 
-static void launch_eq_dense(crdt_ctx *ctx, EqDensePlan p) {
+void launch_eq_dense(crdt_ctx *ctx, EqDensePlan p) {
   const size_t N = p.N;
   // 16-byte pieces: every row of both sides starts on a 16-byte boundary and has an even length
   const bool vc = p.A % 2 == 0 && eq_al16(p.x.clock) && eq_al16(p.y.clock) && (N == 1 || (p.x.cs % 2 == 0 && p.y.cs % 2 == 0));
@@ -542,7 +419,7 @@ static void launch_eq_dense(crdt_ctx *ctx, EqDensePlan p) {
   else hipLaunchKernelGGL((eq_dense_kernel<false, false>), dim3(grid), dim3(kBlock), 0, s, p);
 }
 
-static void launch_eq_deferred(crdt_ctx *ctx, const EqDefPlan &p) {
+void launch_eq_deferred(crdt_ctx *ctx, const EqDefPlan &p) {
   const unsigned long long want = (p.N + kBlock / kWave - 1) / (kBlock / kWave);
   const unsigned grid = (unsigned)std::min<unsigned long long>(want, (unsigned long long)ctx->cu_count * 32);
   hipLaunchKernelGGL(eq_deferred_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, p);
