@@ -534,7 +534,8 @@ typedef struct crdt_map_deferred {
  * written from slot 0, empty slots zeroed).  Deferred removes as crdt_orswot_merge_batch over key
  * bitmaps.  status[s]: bit 0 = deferred slots exhausted, bit 2 = invalid def_count (untouched),
  * bit 4 = some register needed more than self's V slots (that key is incomplete).
- * Limits: A <= 1024, 1 <= V <= 32 on each side (Dcap is not bounded). */
+ * Limits: A <= 1024, 1 <= V <= 64 on each side (Dcap is not bounded); a side past 32 slots takes
+ * the generic one-wave-per-key kernel with 64-bit slot masks. */
 int crdt_map_merge_batch(crdt_ctx *ctx, const crdt_map_states *self, const crdt_map_deferred *self_def,
                          const crdt_map_states *other, const crdt_map_deferred *other_def, uint32_t *status);
 
@@ -1029,13 +1030,21 @@ int crdt_map_nested_merge_batch(crdt_ctx *ctx, const crdt_map_nested_states *sel
  *                clk_pool[clk_row[o]*A ..], val: val[o] }; status[i] bit 1 = an op's clk_row out
  *                of range (skipped), bit 3 = op_off invalid (register untouched), bit 4 = more than
  *                V values.
- * Limits: A <= 1024, 1 <= V <= 16 (lub_many: Vout <= 16); A > 256 or V > 8 run one workgroup of
- * ceil(A / 64) waves per register.  lub_many with 17 <= Vstate <= 64 adds a deep pass: Vout may go up
- * to 64, the registers whose 16-value state overflows are marked instead of reported and folded
- * again, in replica order, with up to Vstate values held in LDS (bit 2 = more than Vstate values at
- * some step).  It needs about Vstate * A * 8 bytes of LDS per register; past 160 KiB, or with
- * Vstate > 64, the call returns CRDT_EUNSUPPORTED before anything is launched.  merge_batch and
- * apply_batch keep their limits. */
+ * Limits: A <= 1024, 1 <= V <= 16 with the working register held in registers, 17 <= V <= 64 with
+ * it held in LDS (below; lub_many: Vout <= 16 unless Vstate >= 17); A > 256 or V > 8 run one
+ * workgroup of ceil(A / 64) waves per register.  lub_many with 17 <= Vstate <= 64 adds a deep
+ * pass: Vout may go up to 64, the registers whose 16-value state overflows are marked instead of
+ * reported and folded again, in replica order, with up to Vstate values held in LDS (bit 2 = more
+ * than Vstate values at some step).  It needs about Vstate * A * 8 bytes of LDS per register; past
+ * 160 KiB, or with Vstate > 64, the call returns CRDT_EUNSUPPORTED before anything is launched.
+ * Registers of 17..64 slots (merge_batch with self's or other's V past 16, apply_batch with V past
+ * 16, lub_many with input V past 16) keep the working register in LDS too, one workgroup of 64..256
+ * threads per register: merge_batch and apply_batch need about V * A * 8 bytes for self's V slots,
+ * lub_many takes input V in 17..64 only with Vstate in 17..64 (every group then runs the LDS fold,
+ * flags as the deep pass reports them) and needs the bytes of Vstate slots; the same 160 KiB bound
+ * holds (V = 64 reaches A = 314), past it CRDT_EUNSUPPORTED naming V, A and the bytes.  When a
+ * register overflows self's V slots (bit 4) the slots hold the first V values of the result.  V > 64
+ * is CRDT_EUNSUPPORTED.  Shapes of 16 slots or fewer run the kernels they always ran. */
 typedef struct crdt_mvreg_states {
   size_t N, A, V;
   uint64_t *vclk;
@@ -1085,9 +1094,10 @@ int crdt_mvreg_apply_batch(crdt_ctx *ctx, const crdt_mvreg_states *states, const
  * clock and value 0; empty slots of the input are skipped wherever they sit.  All of a register's
  * slots are loaded before any is stored, so the compaction in place is safe.  A register the forget
  * leaves bit-identical is not written.  status[i] (device u32, may be NULL) is written for every i;
- * no bit is defined yet: 0.  Limits as merge_batch / apply_batch: A <= 1024, 1 <= V <= 16; A > 256
- * or V > 8 run one workgroup per register, below that a register takes a sub-wave lane segment
- * (one lane per 16 bytes of a row). */
+ * no bit is defined yet: 0.  Limits: A <= 1024, 1 <= V <= 64 (no LDS state, so every A at every V);
+ * A > 256 or V > 8 run one workgroup per register (past 16 slots in two passes over the rows, a
+ * thread moving only its own actor column, so the order in place stays safe), below that a register
+ * takes a sub-wave lane segment (one lane per 16 bytes of a row). */
 int crdt_mvreg_forget_batch(crdt_ctx *ctx, const crdt_mvreg_states *states, const uint64_t *y, size_t y_stride,
                             uint32_t *status);
 
@@ -1113,8 +1123,8 @@ int crdt_mvreg_forget_batch(crdt_ctx *ctx, const crdt_mvreg_states *states, cons
  *    same clock union their sets, as merge_batch treats them; a slot with an empty set is still a key
  *    of the map ({c: {}} != {}, as in the reference's HashMap).  Bits past M / K in a bitmap's last
  *    word are zero by the layout's invariant and are not masked.
- * Limits (those of the matching merge_batch; past them CRDT_EUNSUPPORTED before any launch):
- * A <= 1024; MVReg 1 <= V <= 16; Map 1 <= V <= 32 on each side.  N, and M / K / A where applicable,
+ * Limits (past them CRDT_EUNSUPPORTED before any launch): A <= 1024; MVReg and Map 1 <= V <= 64 on
+ * each side (the compare keeps no LDS state, so every A at every V).  N, and M / K / A where applicable,
  * must match across the sides (CRDT_EINVAL).  Dcap and def_count are not bounded: the result is exact
  * for any number of live slots.  N == 0 returns CRDT_OK.  Device memory only.  A deferred side with
  * Dcap == 0 may pass NULL buffers (crdt_map_eq_batch: a NULL crdt_map_deferred); a def_count that IS

@@ -410,7 +410,7 @@ def merge_batch(self_states: MapStates, other: MapStates, ctx: Optional[Context]
     """self[i].merge(other[i]) for every i, in place on `self_states` (Map::merge map.rs:140-220 with
     MVReg::merge mvreg.rs:112-128), exact for any pair of states.  Returns status (N,) int32:
     bit 0 = deferred slots exhausted, bit 2 = invalid def_count, bit 4 = a register needed more
-    than self's V value slots."""
+    than self's V value slots.  V <= 64 on each side (they may differ)."""
     ctx = ctx or Context.default(self_states.clock.device.index)
     a, ad = _map_states_structs(ctx, self_states, "map.merge_batch(self)")
     b, bd = _map_states_structs(ctx, other, "map.merge_batch(other)")
@@ -424,7 +424,7 @@ def merge_batch(self_states: MapStates, other: MapStates, ctx: Optional[Context]
 
 def eq_batch(x: MapStates, y: MapStates, ctx: Optional[Context] = None) -> torch.Tensor:
     """x[i] == y[i] by Map's derived PartialEq (map.rs:31-47) with MVReg's order-free one per key
-    (mvreg.rs:62-86); V and Dcap may differ between the sides.  Returns ne (N,) int32: 0 = equal, else
+    (mvreg.rs:62-86); V (<= 64 a side) and Dcap may differ between the sides.  Returns ne (N,) int32: 0 = equal, else
     the OR of NE_CLOCK / NE_ENTRIES / NE_VALUES / NE_DEFERRED for every component that differs, or
     NE_INVALID alone when a def_count is above its Dcap.  Both sides are read only."""
     ctx = ctx or Context.default(x.clock.device.index)

@@ -10,6 +10,10 @@ Dense register (the value layout of the Map entry points): slots in Vec order,
     read(vclk (N, V, A), vval)                       reg[i].read() as a ReadCtx              (mvreg.rs:183-215)
     forget_batch(vclk (N, V, A), vval, y)            reg[i].forget(y or y[i]), in place      (mvreg.rs:88-104)
     eq_batch(x (N, Vx, A), x_vval, y (N, Vy, A), y_vval)  x[i] == y[i], order-free            (mvreg.rs:62-86)
+Every call takes registers of up to V = 64 slots.  Past 16 slots merge_batch, apply_batch and lub_many
+keep the working register in LDS (about V * A * 8 bytes within 160 KiB: V = 64 reaches A = 314; past
+that CrdtGpuError with CRDT_EUNSUPPORTED); forget_batch and eq_batch keep no state and take A <= 1024
+at every V.
 The wire forms (register frames, Vec<Op::Put> frames) are in wire.py: mvreg_ingest / mvreg_egress /
 mvreg_ops_ingest / mvreg_ops_egress.
 """
@@ -53,7 +57,8 @@ def lub_many(vclk: torch.Tensor, vval: torch.Tensor, vout: int = 4, ctx: Optiona
     """Left fold of each group's replicas from MVReg::new().  A group needing more than `vout`
     values raises MVRegCapacityError (check=True); a fold state overflow reruns with 16 slots.
     `vstate` = 17..64 asks for the deep pass (registers that overflow 16 values are folded again with
-    `vstate` slots); `vout` may then go up to 64 instead of 16."""
+    `vstate` slots); `vout` may then go up to 64 instead of 16.  Input registers of V = 17..64 slots
+    (a deep fold's own output, for one) need `vstate` = 17..64: every group then folds in LDS."""
     ctx = ctx or Context.default(vclk.device.index)
     squeeze = vclk.dim() == 3
     vc = vclk.unsqueeze(0) if squeeze else vclk
@@ -94,7 +99,7 @@ def _states(ctx, vclk, vval, what):
 def merge_batch(self_vclk: torch.Tensor, self_vval: torch.Tensor, other_vclk: torch.Tensor,
                 other_vval: torch.Tensor, ctx: Optional[Context] = None) -> torch.Tensor:
     """self[i].merge(other[i]) in place on (N, V, A) / (N, V); returns status (N,) int32 (bit 4 =
-    more than self's V values: that register is incomplete)."""
+    more than self's V values: that register is incomplete).  V <= 64 on both sides, which may differ."""
     ctx = ctx or Context.default(self_vclk.device.index)
     a = _states(ctx, self_vclk, self_vval, "mvreg.merge_batch(self)")
     b = _states(ctx, other_vclk, other_vval, "mvreg.merge_batch(other)")
@@ -149,7 +154,8 @@ def encode_ops(streams: Sequence, A: int, device) -> MVRegOpBatch:
 
 
 def apply_batch(vclk: torch.Tensor, vval: torch.Tensor, ops: MVRegOpBatch, ctx: Optional[Context] = None) -> torch.Tensor:
-    """Apply every register's op stream in place; returns status (N,) int32 (include/crdt_gpu.h)."""
+    """Apply every register's op stream in place; returns status (N,) int32 (include/crdt_gpu.h).
+    V <= 64."""
     ctx = ctx or Context.default(vclk.device.index)
     st = _states(ctx, vclk, vval, "mvreg.apply_batch")
     n = ops.val.shape[0]

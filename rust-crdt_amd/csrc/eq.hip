@@ -29,7 +29,8 @@
 //                       runs the VM x VM search (one 64-bit pair mask per lane, one more reduce).
 //   eq_reg_wide_kernel  A > 256 or V > 8: a workgroup per register, thread t = actor t, the same masks
 //                       reduced over the workgroup; unmatched slots search the other side's slots by
-//                       re-reading them.
+//                       re-reading them.  The slot masks are u32 words up to 32 slots a side and u64
+//                       words for 33..64.
 // The Map's register kernels have K owners per state, so a key that differs ORs its bits into ne[s]
 // with an atomic; keys that are equal (the stream's common case) write nothing.
 // The loads, the plans of the dense and deferred kernels and the list compare itself
@@ -314,8 +315,8 @@ __global__ __launch_bounds__(kBlock) void eq_reg_kernel(EqRegPlan p) {
 }
 
 // Workgroup-wide OR of NW words; every thread gets the result.  red: [16][NW].
-template <int NW>
-__device__ __forceinline__ void eq_block_or(unsigned (&v)[NW], unsigned *red) {
+template <int NW, typename M>
+__device__ __forceinline__ void eq_block_or(M (&v)[NW], M *red) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1)
 #pragma unroll
@@ -332,10 +333,11 @@ __device__ __forceinline__ void eq_block_or(unsigned (&v)[NW], unsigned *red) {
     for (int w = 0; w < NW; ++w) v[w] |= red[x * NW + w];
 }
 
-// One workgroup per register (A > 256 or V > 8): thread t = actor t, up to 32 slots a side.
-template <bool MAP>
+// One workgroup per register (A > 256 or V > 8): thread t = actor t; M is the slot mask, u32 for up
+// to 32 slots a side and u64 for up to 64.
+template <bool MAP, typename M>
 __global__ __launch_bounds__(1024) void eq_reg_wide_kernel(EqRegPlan p) {
-  __shared__ unsigned red[16 * 4];
+  __shared__ M red[16 * 4];
   const unsigned t = threadIdx.x;
   const unsigned long long A = p.A, NR = p.N * p.K;
   const unsigned Vx = (unsigned)p.x.V, Vy = (unsigned)p.y.V, Vm = Vx > Vy ? Vx : Vy;
@@ -344,34 +346,34 @@ __global__ __launch_bounds__(1024) void eq_reg_wide_kernel(EqRegPlan p) {
     const unsigned long long s = MAP ? r / p.K : r, k = MAP ? r - s * p.K : 0;
     const u64 *xr = p.x.vclk + s * p.x.cs + k * Vx * A, *yr = p.y.vclk + s * p.y.cs + k * Vy * A;
     const u64 *xv = p.x.vval + s * p.x.vs + k * Vx, *yv = p.y.vval + s * p.y.vs + k * Vy;
-    unsigned v[4] = {0, 0, 0, 0};  // non-empty slots of x, of y, slot s differs from slot s, entry-row bits
+    M v[4] = {0, 0, 0, 0};  // non-empty slots of x, of y, slot s differs from slot s, entry-row bits
     if (MAP) {
       const u64 e = on ? eq_ld1(p.x.ec + s * p.x.es + k * A + t) : 0, f = on ? eq_ld1(p.y.ec + s * p.y.es + k * A + t) : 0;
       v[3] = (e != f ? 1u : 0u) | (e ? 2u : 0u) | (f ? 4u : 0u);
     }
     for (unsigned q = 0; q < Vm; ++q) {
       const u64 a = (on && q < Vx) ? eq_ld1(xr + q * A + t) : 0, b = (on && q < Vy) ? eq_ld1(yr + q * A + t) : 0;
-      if (a) v[0] |= 1u << q;
-      if (b) v[1] |= 1u << q;
-      if (a != b) v[2] |= 1u << q;
+      if (a) v[0] |= M(1) << q;
+      if (b) v[1] |= M(1) << q;
+      if (a != b) v[2] |= M(1) << q;
     }
-    eq_block_or<4>(v, red);
-    const unsigned nzx = (!MAP || (v[3] & 2u)) ? v[0] : 0u, nzy = (!MAP || (v[3] & 4u)) ? v[1] : 0u;
-    unsigned ux = 0, uy = 0;  // slots not settled by slot s against slot s
+    eq_block_or<4, M>(v, red);
+    const M nzx = (!MAP || (v[3] & 2u)) ? v[0] : M(0), nzy = (!MAP || (v[3] & 4u)) ? v[1] : M(0);
+    M ux = 0, uy = 0;  // slots not settled by slot s against slot s
     for (unsigned q = 0; q < Vm; ++q) {
       const bool bx = (nzx >> q) & 1u, by = (nzy >> q) & 1u;
       const bool same = bx && by && !((v[2] >> q) & 1u) && xv[q] == yv[q];
-      if (bx && !same) ux |= 1u << q;
-      if (by && !same) uy |= 1u << q;
+      if (bx && !same) ux |= M(1) << q;
+      if (by && !same) uy |= M(1) << q;
     }
     bool vne = false;
     for (unsigned q = 0; q < Vx && !vne; ++q) {  // an unsettled slot of x searches y's slots
       if (!((ux >> q) & 1u)) continue;
       const u64 a = on ? xr[q * A + t] : 0;
-      unsigned d[1] = {0};
+      M d[1] = {0};
       for (unsigned j = 0; j < Vy; ++j)
-        if (!((nzy >> j) & 1u) || a != (on ? yr[j * A + t] : 0)) d[0] |= 1u << j;
-      eq_block_or<1>(d, red);
+        if (!((nzy >> j) & 1u) || a != (on ? yr[j * A + t] : 0)) d[0] |= M(1) << j;
+      eq_block_or<1, M>(d, red);
       bool found = false;
       for (unsigned j = 0; j < Vy; ++j) found |= !((d[0] >> j) & 1u) && xv[q] == yv[j];
       vne = !found;
@@ -379,10 +381,10 @@ __global__ __launch_bounds__(1024) void eq_reg_wide_kernel(EqRegPlan p) {
     for (unsigned j = 0; j < Vy && !vne; ++j) {
       if (!((uy >> j) & 1u)) continue;
       const u64 b = on ? yr[j * A + t] : 0;
-      unsigned d[1] = {0};
+      M d[1] = {0};
       for (unsigned q = 0; q < Vx; ++q)
-        if (!((nzx >> q) & 1u) || b != (on ? xr[q * A + t] : 0)) d[0] |= 1u << q;
-      eq_block_or<1>(d, red);
+        if (!((nzx >> q) & 1u) || b != (on ? xr[q * A + t] : 0)) d[0] |= M(1) << q;
+      eq_block_or<1, M>(d, red);
       bool found = false;
       for (unsigned q = 0; q < Vx; ++q) found |= !((d[0] >> q) & 1u) && xv[q] == yv[j];
       vne = !found;
@@ -439,7 +441,8 @@ static void launch_eq_reg(crdt_ctx *ctx, EqRegPlan p) {
   if (A > 256 || Vm > 8) {
     const unsigned nt = (unsigned)std::max<size_t>(64, (A + 63) / 64 * 64);
     const unsigned grid = (unsigned)std::min<unsigned long long>(NR, 0x7fffffffull);
-    hipLaunchKernelGGL((eq_reg_wide_kernel<MAP>), dim3(grid), dim3(nt), 0, s, p);
+    if (Vm > 32) hipLaunchKernelGGL((eq_reg_wide_kernel<MAP, u64>), dim3(grid), dim3(nt), 0, s, p);
+    else hipLaunchKernelGGL((eq_reg_wide_kernel<MAP, unsigned>), dim3(grid), dim3(nt), 0, s, p);
     return;
   }
   bool vec = A % 2 == 0 && eq_al16(p.x.vclk) && eq_al16(p.y.vclk) && (p.N == 1 || (p.x.cs % 2 == 0 && p.y.cs % 2 == 0));
@@ -474,7 +477,7 @@ int crdt_mvreg_eq_batch(crdt_ctx *ctx, const crdt_mvreg_states *x, const crdt_mv
   if (N == 0) return CRDT_OK;
   if (A > 1024) return fail(ctx, CRDT_EUNSUPPORTED, "mvreg_eq_batch: A = %zu > 1024 actors", A);
   for (const crdt_mvreg_states *st : {x, y}) {
-    if (st->V == 0 || st->V > 16) return fail(ctx, CRDT_EUNSUPPORTED, "mvreg_eq_batch: V = %zu not in [1, 16]", st->V);
+    if (st->V == 0 || st->V > 64) return fail(ctx, CRDT_EUNSUPPORTED, "mvreg_eq_batch: V = %zu not in [1, 64]", st->V);
     if (A && (!st->vclk || !st->vval)) return fail(ctx, CRDT_EINVAL, "mvreg_eq_batch: NULL register buffers");
     if (N > 1 && (st->vclk_stride < st->V * A || st->vval_stride < st->V))
       return fail(ctx, CRDT_EINVAL, "mvreg_eq_batch: strides below the register size");
@@ -562,7 +565,7 @@ int crdt_map_eq_batch(crdt_ctx *ctx, const crdt_map_states *x, const crdt_map_de
   for (int side = 0; side < 2; ++side) {
     const crdt_map_states *st = side ? y : x;
     const crdt_map_deferred *df = side ? yd : xd;
-    if (st->V == 0 || st->V > 32) return fail(ctx, CRDT_EUNSUPPORTED, "map_eq_batch: V = %zu not in [1, 32]", st->V);
+    if (st->V == 0 || st->V > 64) return fail(ctx, CRDT_EUNSUPPORTED, "map_eq_batch: V = %zu not in [1, 64]", st->V);
     if (A && (!st->clock || (K && (!st->ec || !st->vclk || !st->vval))))
       return fail(ctx, CRDT_EINVAL, "map_eq_batch: NULL state buffers");
     if (N > 1 && (st->clock_stride < A || st->ec_stride < K * A || st->vclk_stride < K * st->V * A ||

@@ -248,7 +248,7 @@ __global__ __launch_bounds__(kBlock) void orswot_pair_join_kernel(OrswotPairPlan
 }
 
 // ---- Map<K, MVReg> key merge --------------------------------------------------------------------
-constexpr int kMapPairMaxV = 32;  // value slots per side (u32 slot masks of the generic kernel)
+constexpr int kMapPairMaxV = 64;  // value slots per side (u64 slot masks of the generic kernel past 32)
 
 struct MapPairPlan {
   unsigned long long N, K, A, V1, V2, Kw;
@@ -337,8 +337,9 @@ __device__ __forceinline__ u64 prl64(u64 x, int l) {
   return ((u64)hi << 32) | lo;
 }
 
-// One wave per (pair, key); APL clock words per lane (A <= 64 * APL).
-template <int APL>
+// One wave per (pair, key); APL clock words per lane (A <= 64 * APL).  SM is the slot mask: u32 for
+// up to 32 value slots a side, u64 for 33..64.
+template <int APL, typename SM = unsigned>
 __global__ __launch_bounds__(kBlock) void map_pair_join_kernel(MapPairPlan p) {
   const int lane = threadIdx.x % kWave;
   const unsigned long long w0 = (blockIdx.x * (unsigned long long)kBlock + threadIdx.x) / kWave;
@@ -359,14 +360,14 @@ __global__ __launch_bounds__(kBlock) void map_pair_join_kernel(MapPairPlan p) {
     if (!p1 && !p2) continue;  // no entry on either side: nothing to merge
     const PRow<APL> c1 = prow<APL>(p.c1 + s * p.c1_s, lane, A), c2 = prow<APL>(p.c2 + s * p.c2_s, lane, A);
     // occupied value slots (Vec order = slot order, empty slot <=> zero clock)
-    unsigned m1 = 0, m2 = 0;
+    SM m1 = 0, m2 = 0;
     for (unsigned q = 0; q < p.V1; ++q)
-      if (pnz(prow<APL>(vc1 + q * A, lane, A))) m1 |= 1u << q;
+      if (pnz(prow<APL>(vc1 + q * A, lane, A))) m1 |= SM(1) << q;
     for (unsigned q = 0; q < p.V2; ++q)
-      if (pnz(prow<APL>(vc2 + q * A, lane, A))) m2 |= 1u << q;
+      if (pnz(prow<APL>(vc2 + q * A, lane, A))) m2 |= SM(1) << q;
     bool present = true;
     PRow<APL> e, X;  // resulting entry clock, forget clock of the values
-    unsigned keep1 = 0, add2 = 0;
+    SM keep1 = 0, add2 = 0;
     if (p1 && !p2) {  // :146-161
       if (ple(e1, c2)) {
         present = false;
@@ -403,7 +404,7 @@ __global__ __launch_bounds__(kBlock) void map_pair_join_kernel(MapPairPlan p) {
           bool dom = false;
           for (unsigned r = 0; r < p.V2 && !dom; ++r)
             if ((m2 >> r) & 1u) dom = plt(x, prow<APL>(vc2 + r * A, lane, A));
-          if (!dom) keep1 |= 1u << q;
+          if (!dom) keep1 |= SM(1) << q;
         }
         for (unsigned r = 0; r < p.V2; ++r) {
           if (!((m2 >> r) & 1u)) continue;
@@ -414,7 +415,7 @@ __global__ __launch_bounds__(kBlock) void map_pair_join_kernel(MapPairPlan p) {
               const PRow<APL> x = prow<APL>(vc1 + q * A, lane, A);
               drop = plt(y, x) || peq(y, x);
             }
-          if (!drop) add2 |= 1u << r;
+          if (!drop) add2 |= SM(1) << r;
         }
         X = pforget(pmax(e1, e2), common);  // information_that_was_deleted
         e = common;
@@ -1038,7 +1039,18 @@ extern "C" int crdt_map_merge_batch(crdt_ctx *ctx, const crdt_map_states *self, 
     const unsigned grid = pair_grid(ctx, (unsigned long long)N * K, ctx->tune.map_pair_bpc);
     timing_begin(ctx, "map_pair_join");
     const bool pf = ctx->tune.map_pair_pf, nt = ctx->tune.map_pair_nt;
-    if (ctx->tune.map_pair_reg && a.V <= 4 && b.V <= 4 && A <= 4 * (size_t)kWave) {  // register-resident rows
+    if (a.V > 32 || b.V > 32) {  // 33..64 value slots on a side: the generic kernel with u64 slot masks
+      if (A <= (size_t)kWave)
+        hipLaunchKernelGGL((map_pair_join_kernel<1, u64>), dim3(grid), dim3(kBlock), 0, ctx->stream, p);
+      else if (A <= 2 * (size_t)kWave)
+        hipLaunchKernelGGL((map_pair_join_kernel<2, u64>), dim3(grid), dim3(kBlock), 0, ctx->stream, p);
+      else if (A <= 4 * (size_t)kWave)
+        hipLaunchKernelGGL((map_pair_join_kernel<4, u64>), dim3(grid), dim3(kBlock), 0, ctx->stream, p);
+      else if (A <= 8 * (size_t)kWave)
+        hipLaunchKernelGGL((map_pair_join_kernel<8, u64>), dim3(grid), dim3(kBlock), 0, ctx->stream, p);
+      else
+        hipLaunchKernelGGL((map_pair_join_kernel<16, u64>), dim3(grid), dim3(kBlock), 0, ctx->stream, p);
+    } else if (ctx->tune.map_pair_reg && a.V <= 4 && b.V <= 4 && A <= 4 * (size_t)kWave) {  // register-resident rows
       if (A <= 16 && ctx->tune.map_pair_reg == 1)
         hipLaunchKernelGGL((pf ? (nt ? map_pair_join_seg_kernel<16, 4, true, true> : map_pair_join_seg_kernel<16, 4, true, false>)
                               : (nt ? map_pair_join_seg_kernel<16, 4, false, true> : map_pair_join_seg_kernel<16, 4, false, false>)),

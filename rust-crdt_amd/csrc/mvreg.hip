@@ -27,7 +27,12 @@
 // whose 16-value state overflowed (instead of flags bit 2), and mvreg_fold_deep_kernel folds each marked
 // register again, in replica order, with up to Vstate values held in LDS (mvreg_lds.hpp, the state the
 // Map fold's deep pass uses, map_deep.hip).
+//
+// Registers of 17..64 value slots (merge_batch with either side past 16, apply_batch, lub_many with
+// input V past 16) go to the LDS-register kernels of mvreg_deep.hip; every shape of 16 slots or
+// fewer takes the kernels of this file.
 #include "common.hpp"
+#include "mvreg_deep.hpp"
 #include "mvreg_lds.hpp"
 
 namespace crdt {
@@ -210,17 +215,6 @@ struct MvReg {
   }
 };
 
-struct MvFoldPlan {
-  const u64 *vclk, *vval;
-  unsigned long long G, R, A, V;
-  unsigned long long c_rs, c_gs, v_rs, v_gs;
-  u64 *o_vclk, *o_vval;
-  unsigned long long Vout;
-  uint32_t *o_nval, *o_flags;
-  uint8_t *mark;  // (nullable) per group: the state overflowed, left to the deep pass
-  unsigned long long Vstate;  // the deep pass's slots
-};
-
 // One group's left fold (one wave per group); the next replica's slots are loaded while this
 // one merges.
 template <int APL, int VS, int VI, bool BLK = false>
@@ -292,15 +286,6 @@ __global__ __launch_bounds__(256) void mvreg_fold_deep_kernel(MvFoldPlan p) {
   }
 }
 
-struct MvPairPlan {
-  u64 *s_vclk, *s_vval;
-  unsigned long long s_cs, s_vs, Vs;
-  const u64 *o_vclk, *o_vval;
-  unsigned long long o_cs, o_vs, Vo;
-  unsigned long long N, A;
-  uint32_t *status;
-};
-
 template <int APL, int VS, int VI, bool BLK = false>
 __global__ __launch_bounds__(BLK ? 1024 : 64) void mvreg_pair_kernel(MvPairPlan p) {
   const int lane = threadIdx.x;
@@ -326,16 +311,6 @@ __global__ __launch_bounds__(BLK ? 1024 : 64) void mvreg_pair_kernel(MvPairPlan 
   const int n = acc.store(p.s_vclk + i * p.s_cs, p.s_vval + i * p.s_vs, p.Vs, p.A, lane, nt);
   if (lane == 0) p.status[i] = ((unsigned long long)n > p.Vs || acc.ovf) ? 16u : 0u;
 }
-
-struct MvApplyPlan {
-  u64 *vclk, *vval;
-  unsigned long long cs, vs, V, N, A;
-  const u64 *op_off;
-  const uint32_t *clk_row;
-  const u64 *clk_pool, *val;
-  unsigned long long n_ops, n_clk_rows;
-  uint32_t *status;
-};
 
 template <int APL, int VS, bool BLK = false>
 __global__ __launch_bounds__(BLK ? 1024 : 64) void mvreg_apply_kernel(MvApplyPlan p) {
@@ -488,13 +463,17 @@ int crdt_mvreg_lub_many(crdt_ctx *ctx, const crdt_mvreg_batch *in, crdt_mvreg_ou
   const size_t vout_max = deep ? (size_t)kLdsMvMax : (size_t)kMvMaxState;
   if (Vout == 0 || Vout > vout_max)
     return fail(ctx, CRDT_EUNSUPPORTED, "mvreg_lub_many: Vout = %zu not in [1, %zu]", Vout, vout_max);
+  // input registers of 17..64 slots: every group takes the LDS kernel (mvreg_deep.hip), no first pass
+  const bool any = V > (size_t)kMvMaxState;
+  if (any && !deep)
+    return fail(ctx, CRDT_EUNSUPPORTED, "mvreg_lub_many: V = %zu > 16 value slots needs Vstate in [17, %d]", V, kLdsMvMax);
   const size_t deep_lds = deep ? lds_mv_bytes(out->Vstate, A) : 0;
   if (deep_lds + kLdsMvRed * sizeof(u64) > 160 * 1024)
     return fail(ctx, CRDT_EUNSUPPORTED, "mvreg_lub_many: Vstate = %zu values of A = %zu actors need %zu bytes of LDS (> 160 KiB)",
                 out->Vstate, A, deep_lds + kLdsMvRed * sizeof(u64));
   if (R > 0 && V > 0 && (!in->vclk || !in->vval)) return fail(ctx, CRDT_EINVAL, "mvreg_lub_many: NULL input");
   if (A > 1024) return fail(ctx, CRDT_EUNSUPPORTED, "mvreg_lub_many: A = %zu > 1024 actors", A);
-  if (V > 16) return fail(ctx, CRDT_EUNSUPPORTED, "mvreg_lub_many: V = %zu > 16 value slots", V);
+  if (V > (size_t)kLdsMvMax) return fail(ctx, CRDT_EUNSUPPORTED, "mvreg_lub_many: V = %zu > %d value slots", V, kLdsMvMax);
   if (G > 0x7fffffffULL) return fail(ctx, CRDT_EUNSUPPORTED, "mvreg_lub_many: G too large");
   if (R > 0 && V > 0 && (in->vclk_rstride < V * A || in->vval_rstride < V))
     return fail(ctx, CRDT_EINVAL, "mvreg_lub_many: replica strides below the register size");
@@ -516,6 +495,7 @@ int crdt_mvreg_lub_many(crdt_ctx *ctx, const crdt_mvreg_batch *in, crdt_mvreg_ou
   p.o_nval = out->nval;
   p.o_flags = out->flags;
   p.Vstate = out->Vstate;
+  if (any) return mvreg_fold_any(ctx, p);
   if (deep) {  // one marker byte per register in the context scratch
     if (int rc = ensure_scratch(ctx, G)) return rc;
     p.mark = static_cast<uint8_t *>(ctx->scratch);
@@ -555,9 +535,9 @@ int crdt_mvreg_merge_batch(crdt_ctx *ctx, const crdt_mvreg_states *self, const c
   const size_t N = self->N, A = self->A;
   if (other->N != N || other->A != A) return fail(ctx, CRDT_EINVAL, "mvreg_merge_batch: self and other differ in N or A");
   if (N == 0 || A == 0) return CRDT_OK;
-  if (self->V == 0 || self->V > 16 || other->V > 16)
-    return fail(ctx, CRDT_EUNSUPPORTED, "mvreg_merge_batch: V must be in [1, 16] (self %zu, other %zu)", self->V,
-                other->V);
+  if (self->V == 0 || self->V > (size_t)kLdsMvMax || other->V > (size_t)kLdsMvMax)
+    return fail(ctx, CRDT_EUNSUPPORTED, "mvreg_merge_batch: V must be in [1, %d] (self %zu, other %zu)", kLdsMvMax,
+                self->V, other->V);
   if (A > 1024) return fail(ctx, CRDT_EUNSUPPORTED, "mvreg_merge_batch: A = %zu > 1024 actors", A);
   if (!self->vclk || !self->vval || (other->V && (!other->vclk || !other->vval)))
     return fail(ctx, CRDT_EINVAL, "mvreg_merge_batch: NULL register buffers");
@@ -577,6 +557,7 @@ int crdt_mvreg_merge_batch(crdt_ctx *ctx, const crdt_mvreg_states *self, const c
   p.N = N;
   p.A = A;
   p.status = status;
+  if (self->V > (size_t)kMvMaxState || other->V > (size_t)kMvMaxState) return mvreg_pair_deep(ctx, p);
   const int VS = mv_vs(self->V + std::max<size_t>(other->V, 1));
   const bool wide = mv_wide(A, std::max(self->V, other->V));
   const int VI = wide ? mv_vi_wide(other->V) : mv_vi(other->V);
@@ -597,7 +578,8 @@ int crdt_mvreg_apply_batch(crdt_ctx *ctx, const crdt_mvreg_states *states, const
   if (!states || !ops || !status) return fail(ctx, CRDT_EINVAL, "mvreg_apply_batch: NULL argument");
   const size_t N = states->N, A = states->A, V = states->V;
   if (N == 0 || A == 0) return CRDT_OK;
-  if (V == 0 || V > 16) return fail(ctx, CRDT_EUNSUPPORTED, "mvreg_apply_batch: V = %zu not in [1, 16]", V);
+  if (V == 0 || V > (size_t)kLdsMvMax)
+    return fail(ctx, CRDT_EUNSUPPORTED, "mvreg_apply_batch: V = %zu not in [1, %d]", V, kLdsMvMax);
   if (A > 1024) return fail(ctx, CRDT_EUNSUPPORTED, "mvreg_apply_batch: A = %zu > 1024 actors", A);
   if (!states->vclk || !states->vval || !ops->op_off)
     return fail(ctx, CRDT_EINVAL, "mvreg_apply_batch: NULL register / op_off buffers");
@@ -620,6 +602,7 @@ int crdt_mvreg_apply_batch(crdt_ctx *ctx, const crdt_mvreg_states *states, const
   p.n_ops = ops->n_ops;
   p.n_clk_rows = ops->n_clk_rows;
   p.status = status;
+  if (V > (size_t)kMvMaxState) return mvreg_apply_deep(ctx, p);
   const int VS = mv_vs(V + 1);
   timing_begin(ctx, "mvreg_apply");
   const int apl = mv_apl(A);

@@ -15,7 +15,8 @@
 // (VEC), in 8-byte words otherwise.
 //
 // Past one wave's shapes (A > 256 or V > 8, the split of mvreg.hip) one workgroup of ceil(A / 64)
-// waves takes a register, thread t = actor t, every vote a workgroup vote.
+// waves takes a register, thread t = actor t, every vote a workgroup vote (up to 16 slots held in
+// registers; 17..64 slots: mvreg_forget_wide64_kernel, two passes over the thread's own column).
 #include "common.hpp"
 
 namespace crdt {
@@ -196,6 +197,68 @@ __global__ __launch_bounds__(1024) void mvreg_forget_wide_kernel(MvForgetPlan p)
   if (t == 0 && p.status) p.status[i] = 0;
 }
 
+// The 64-slot form (16 < V <= 64): thread t = actor t again, but the rows are not held in registers.
+// Pass 1 reads the thread's column (eight slots' loads in flight) and votes the surviving slots into one
+// u64 mask; pass 2 reads the column again, eight slots at a time, and compacts the survivors in Vec order.  A thread touches only its own actor column
+// and the write slot never passes the read slot (d <= s), so the in-place order is safe without a
+// barrier between the passes; thread 0 alone moves the values, in the same order.  A word is written
+// only where it changes.
+__global__ __launch_bounds__(1024) void mvreg_forget_wide64_kernel(MvForgetPlan p) {
+  __shared__ u64 red[1024 / kWave];
+  const unsigned t = threadIdx.x;
+  const unsigned long long i = blockIdx.x, A = p.A, V = p.V;
+  u64 *rc = p.vclk + i * p.cs, *rv = p.vval + i * p.vs;
+  const bool on = t < A;
+  const u64 yv = on ? p.y[i * p.ys + t] : 0;
+  u64 had = 0, surv = 0;  // my column: slot non-zero before / after the forget
+  constexpr unsigned GR = 8;  // slots whose loads are issued together
+  for (unsigned long long s0 = 0; s0 < V; s0 += GR) {
+    u64 c[GR];
+#pragma unroll
+    for (unsigned u = 0; u < GR; ++u) c[u] = (on && s0 + u < V) ? rc[(s0 + u) * A + t] : 0;
+#pragma unroll
+    for (unsigned u = 0; u < GR; ++u) {
+      if (c[u] != 0) had |= 1ull << (s0 + u);
+      if (c[u] > yv) surv |= 1ull << (s0 + u);
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) surv |= __shfl_xor(surv, off, kWave);
+  const unsigned nw = blockDim.x / kWave;
+  if (nw > 1) {  // (workgroup-uniform)
+    if (t % kWave == 0) red[t / kWave] = surv;
+    __syncthreads();
+    for (unsigned x = 0; x < nw; ++x) surv |= red[x];
+  }
+  const unsigned long long n = (unsigned long long)__popcll(surv);
+  // a group's loads come before its stores, and its stores go to slots at or below the group's own
+  for (unsigned long long s0 = 0; s0 < V; s0 += GR) {
+    if (!((surv >> s0) & ((1ull << GR) - 1))) continue;
+    u64 c[GR];
+#pragma unroll
+    for (unsigned u = 0; u < GR; ++u) c[u] = (on && s0 + u < V) ? rc[(s0 + u) * A + t] : 0;
+    u64 vv[GR];
+    if (t == 0) {
+#pragma unroll
+      for (unsigned u = 0; u < GR; ++u) vv[u] = s0 + u < V ? rv[s0 + u] : 0;
+    }
+#pragma unroll
+    for (unsigned u = 0; u < GR; ++u) {
+      const unsigned long long s = s0 + u;
+      if (s >= V || !((surv >> s) & 1)) continue;
+      const unsigned long long d = (unsigned long long)__popcll(surv & ((1ull << s) - 1));
+      const u64 k = c[u] > yv ? c[u] : 0;
+      if (on && (d != s || k != c[u])) rc[d * A + t] = k;
+      if (t == 0 && d != s) rv[d] = vv[u];
+    }
+  }
+  for (unsigned long long s = n; s < V; ++s) {
+    if ((had >> s) & 1) rc[s * A + t] = 0;
+    if (t == 0) rv[s] = 0;
+  }
+  if (t == 0 && p.status) p.status[i] = 0;
+}
+
 template <int G, int CH, int VM>
 static void launch_forget_vec(const MvForgetPlan &p, bool vec, unsigned grid, hipStream_t s) {
   if (vec) hipLaunchKernelGGL((mvreg_forget_kernel<G, CH, VM, true>), dim3(grid), dim3(kBlock), 0, s, p);
@@ -228,7 +291,7 @@ int crdt_mvreg_forget_batch(crdt_ctx *ctx, const crdt_mvreg_states *states, cons
   if (!states) return fail(ctx, CRDT_EINVAL, "mvreg_forget_batch: NULL states");
   const size_t N = states->N, A = states->A, V = states->V;
   if (N == 0 || A == 0) return CRDT_OK;
-  if (V == 0 || V > 16) return fail(ctx, CRDT_EUNSUPPORTED, "mvreg_forget_batch: V = %zu not in [1, 16]", V);
+  if (V == 0 || V > 64) return fail(ctx, CRDT_EUNSUPPORTED, "mvreg_forget_batch: V = %zu not in [1, 64]", V);
   if (A > 1024) return fail(ctx, CRDT_EUNSUPPORTED, "mvreg_forget_batch: A = %zu > 1024 actors", A);
   if (!states->vclk || !states->vval || !y) return fail(ctx, CRDT_EINVAL, "mvreg_forget_batch: NULL register buffers / y");
   if (N > 1 && (states->vclk_stride < V * A || states->vval_stride < V))
@@ -250,7 +313,8 @@ int crdt_mvreg_forget_batch(crdt_ctx *ctx, const crdt_mvreg_states *states, cons
   timing_begin(ctx, "mvreg_forget");
   if (A > 256 || V > 8) {
     const unsigned nt = (unsigned)std::max<size_t>(64, (A + 63) / 64 * 64);
-    hipLaunchKernelGGL(mvreg_forget_wide_kernel, dim3((unsigned)N), dim3(nt), 0, ctx->stream, p);
+    if (V > 16) hipLaunchKernelGGL(mvreg_forget_wide64_kernel, dim3((unsigned)N), dim3(nt), 0, ctx->stream, p);
+    else hipLaunchKernelGGL(mvreg_forget_wide_kernel, dim3((unsigned)N), dim3(nt), 0, ctx->stream, p);
   } else {
     // 16-byte pieces: every row and y row starts on a 16-byte boundary
     const bool vec = A % 2 == 0 && ((uintptr_t)p.vclk % 16 == 0) && (N == 1 || p.cs % 2 == 0) &&

@@ -185,6 +185,118 @@ struct LdsMv {
       }
   }
 
+  // Load a dense register of V <= VS slots: slot s of the state is slot s of the input (Vec order =
+  // slot order), an all-zero row stays a free slot.  One vote round.
+  __device__ __forceinline__ void load(const u64 *rows, const u64 *vals, unsigned long long V, u64 *red) {
+    u64 a[1] = {~0ull}, o[1] = {0};
+    for (unsigned long long s = 0; s < V; ++s) {
+      u64 x[kLdsMvApt];
+      if (load_row(x, rows + s * A)) o[0] |= 1ull << s;
+#pragma unroll
+      for (int j = 0; j < kLdsMvApt; ++j)
+        if (on[j]) vc[(size_t)s * A + act[j]] = x[j];
+      if (threadIdx.x == 0) {
+        val[s] = vals[s];
+        seq[s] = s;
+      }
+    }
+    wide_vote<0, 1>(a, o, red);
+    used = o[0];
+    next = V;
+  }
+
+  // bit q of le_qx = "slot q <= x on my actors", of le_xq = "x <= slot q", over the slots of `mask`
+  // (the walk of merge(); the bits of the other slots stay set)
+  __device__ __forceinline__ void cmp_slots(u64 mask, const u64 (&x)[kLdsMvApt], u64 &le_qx, u64 &le_xq) const {
+    le_qx = le_xq = ~0ull;
+    for (unsigned q0 = 0; q0 < VS; q0 += kLdsMvWalk) {
+      const unsigned um = (unsigned)(mask >> q0) & ((1u << kLdsMvWalk) - 1u);
+      if (!um) continue;
+      u64 c[kLdsMvWalk][kLdsMvApt];
+#pragma unroll
+      for (int u = 0; u < kLdsMvWalk; ++u)
+#pragma unroll
+        for (int j = 0; j < kLdsMvApt; ++j)
+          c[u][j] = (on[j] && q0 + u < VS) ? vc[(size_t)(q0 + u) * A + act[j]] : 0;
+#pragma unroll
+      for (int u = 0; u < kLdsMvWalk; ++u) {
+        bool l1 = true, l2 = true;
+#pragma unroll
+        for (int j = 0; j < kLdsMvApt; ++j) {  // (an actor past A: c = x = 0)
+          l1 &= c[u][j] <= x[j];
+          l2 &= x[j] <= c[u][j];
+        }
+        if (((um >> u) & 1) && !l1) le_qx &= ~(1ull << (q0 + u));
+        if (((um >> u) & 1) && !l2) le_xq &= ~(1ull << (q0 + u));
+      }
+    }
+  }
+
+  // self.merge(other) for other's V <= 64 value rows (empty rows skipped), in chunks of kLdsMvVin.
+  // other's values are never compared with each other (mvreg.rs:113-126), so the chunks cannot be
+  // merged one after the other: pass 1 collects, over all chunks, the own slots strictly below some
+  // incoming value; pass 2 tests every incoming value against the FIXED mask of kept own slots (never
+  // against a slot appended during the pass) and appends in incoming order.  One vote per chunk and pass.
+  __device__ __forceinline__ void merge_any(const u64 *rows, const u64 *vals, unsigned long long V, u64 *red) {
+    constexpr int VIN = kLdsMvVin;
+    const u64 own = used;
+    u64 drop = 0, v2m = 0;
+    for (unsigned long long t0 = 0; t0 < V; t0 += VIN) {
+      u64 a[2 * VIN], o[1] = {0};
+#pragma unroll
+      for (int w = 0; w < 2 * VIN; ++w) a[w] = ~0ull;
+#pragma unroll
+      for (int t = 0; t < VIN; ++t)
+        if (t0 + t < V) {
+          u64 x[kLdsMvApt];
+          if (load_row(x, rows + (size_t)(t0 + t) * A)) o[0] |= 1ull << t;
+          cmp_slots(own, x, a[t], a[VIN + t]);
+        }
+      wide_vote<2 * VIN, 1>(a, o, red);
+#pragma unroll
+      for (int t = 0; t < VIN; ++t)  // own < some incoming value: dropped
+        if ((o[0] >> t) & 1) drop |= a[t] & ~a[VIN + t];
+      v2m |= o[0] << t0;
+    }
+    const u64 keep = own & ~drop;
+    used = keep;
+    for (unsigned long long t0 = 0; t0 < V; t0 += VIN) {
+      u64 a[VIN], o[1] = {0};
+#pragma unroll
+      for (int w = 0; w < VIN; ++w) a[w] = ~0ull;
+#pragma unroll
+      for (int t = 0; t < VIN; ++t)
+        if (t0 + t < V && ((v2m >> (t0 + t)) & 1)) {
+          u64 x[kLdsMvApt], le_qx;
+          load_row(x, rows + (size_t)(t0 + t) * A);
+          cmp_slots(keep, x, le_qx, a[t]);
+        }
+      wide_vote<VIN, 0>(a, o, red);
+#pragma unroll
+      for (int t = 0; t < VIN; ++t)  // incoming <= a KEPT own value: not added
+        if (t0 + t < V && ((v2m >> (t0 + t)) & 1) && !(a[t] & keep)) {
+          u64 x[kLdsMvApt];
+          load_row(x, rows + (size_t)(t0 + t) * A);
+          append(x, vals[t0 + t]);
+        }
+    }
+  }
+
+  // self.apply(Op::Put { clock: x, val: v }) (mvreg.rs:130-166): one vote gives "slot <= x" and
+  // "slot >= x" over all slots.  The slots <= x go (Less or Equal); the Put is pushed unless a
+  // remaining slot is >= x (then strictly greater).  An empty clock is a no-op.
+  __device__ __forceinline__ void apply_put(const u64 (&x)[kLdsMvApt], u64 v, u64 *red) {
+    u64 a[2], o[1] = {0};
+    cmp_slots(used, x, a[0], a[1]);
+#pragma unroll
+    for (int j = 0; j < kLdsMvApt; ++j)
+      if (x[j] != 0) o[0] = 1;
+    wide_vote<2, 1>(a, o, red);
+    if (!o[0]) return;  // (workgroup-uniform)
+    used &= ~a[0];
+    if (!(a[1] & used)) append(x, v);
+  }
+
   // Write the register to Vout slots in Vec order (ascending sequence number, the rest zeroed).
   __device__ __forceinline__ void store(u64 *o_vclk, u64 *o_vval, unsigned long long Vout) {
     __syncthreads();  // seq (thread 0's writes) visible

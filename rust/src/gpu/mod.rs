@@ -158,8 +158,9 @@ pub trait BatchCvRDT: CvRDT + Sized {
 /// Capacity limits of the library this module binds (include/crdt_gpu.h; checked against the
 /// header's stated limits by tests/test_rust_shim.py).  Past them a call returns `GpuError` with
 /// `CRDT_EUNSUPPORTED` and leaves its inputs untouched.
-/// Values per MVReg register (`crdt_map_lub_many`: V <= 16; `crdt_mvreg_*`: V <= 16;
-/// `crdt_map_merge_batch` takes up to 32 per side, the smallest limit is the one checked here).
+/// Values per MVReg register (`crdt_map_lub_many`: input V <= 16; `crdt_mvreg_*`,
+/// `crdt_map_merge_batch` and `crdt_map_eq_batch` take up to 64 per side, past 16 with the register
+/// in LDS; the smallest limit is the one checked here).
 pub const MAP_MAX_VALUES: usize = 16;
 /// Actors of the Map, MVReg and Orswot-apply kernels (A <= 1024).
 pub const MAP_MAX_ACTORS: usize = 1024;
