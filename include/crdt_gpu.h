@@ -1182,6 +1182,78 @@ int crdt_map_orswot_eq_batch(crdt_ctx *ctx, const crdt_map_orswot_states *x, con
 int crdt_map_nested_eq_batch(crdt_ctx *ctx, const crdt_map_nested_states *x, const crdt_map_deferred *xd,
                              const crdt_map_nested_states *y, const crdt_map_deferred *yd, uint32_t *ne);
 
+/* ---- re-index resident states when a dictionary or a capacity grows ------------------------------
+ * Out-of-place gathers of N dense states from one layout into another along every indexed axis
+ * (actor columns, member / key rows and bits, value slots, deferred slots), on the device, without a
+ * host synchronisation.  They are what a caller keeping states resident runs when an ingest reports an
+ * id missing from its dictionary (status bit 1) or a call reports a capacity ("retry with a larger
+ * Dcap" / "more slots", bits 0 and 4): build the union dictionary, crdt_reindex_map_*, reindex, retry.
+ *
+ * Axis map: a device uint32_t src[n_out].  Output index j takes the data of input index src[j]; any
+ * src[j] >= n_in means nobody (zeros: an absent member / key).  A NULL map is the identity on
+ * min(n_in, n_out) indices and nobody past it (the pure capacity change).  A map that is not injective
+ * gives the gather's result (an input index copied to several outputs); this is not checked.
+ *   crdt_reindex_map_u32 / _u64: old_ids[n_old] and new_ids[n_new] ascending and unique, as the ingest
+ *   calls require; src[j] = position of new_ids[j] in old_ids, or 0xFFFFFFFF when absent; *n_lost
+ *   (device u32[1]) = the number of old ids absent from new_ids.  One lane per new id, a binary search.
+ *
+ * Layout calls (every output word of every state is written, so out needs no zeroing; gaps between
+ * strided rows are not touched; in is read only; overlapping in and out is undefined, and equal base
+ * pointers return CRDT_EINVAL):
+ *   crdt_rows_reindex    N rows of planes x A_in u64 words (plane q of row i at in + i*in_stride +
+ *                        q*A_in) into rows of planes x A_out: planes = 1 for VClock / GCounter rows and
+ *                        pooled def_clock[D][A] rows, 2 for PNCounter's P and N halves.
+ *   crdt_bitmap_reindex  N bitmap rows of U_in bits into U_out bits, bit by bit (GSet rows, pooled
+ *                        def_members[D][Mw] / def_keys[D][Kw] rows; strides in words).  Bits past U_out
+ *                        in the last output word are written 0 (the layout's invariant).
+ *   crdt_orswot_reindex  clock and entry columns by actor_src, entry rows by member_src, the first
+ *                        def_count[s] deferred slots (clock columns, member bits; slot order kept) and
+ *                        def_count.  out's M, A and Dcap may each be larger or smaller than in's; Dcap
+ *                        == 0 with NULL deferred buffers is accepted on either side (an input def_count
+ *                        that IS passed is read whatever Dcap is).
+ *   crdt_mvreg_reindex   value clocks by actor_src, slot v to slot v (positions and holes kept); slots
+ *                        in [V_in, V_out) are zeroed.
+ *   crdt_map_reindex     clock, ec[K][A], vclk[K][V][A], vval[K][V], deferred clocks and key bitmaps; K,
+ *                        A, V and Dcap may each differ between the sides; a NULL crdt_map_deferred means
+ *                        no slots on that side.
+ * status[s] (device u32[N], may be NULL; written for every s):
+ *   CRDT_REINDEX_DCAP     def_count[s] > out Dcap: the first out Dcap slots are kept, the output count
+ *                         is out Dcap.
+ *   CRDT_REINDEX_DROPPED  an id the map drops (no output index takes it) held data in state s: a
+ *                         non-zero counter in a dropped actor column of the clock, of an entry row, of a
+ *                         value clock in a kept slot of a kept key, or of one of the def_count[s]
+ *                         deferred clocks; a non-zero entry row of a dropped member / key; a bit set for
+ *                         a dropped member / key in one of the def_count[s] deferred bitmaps.
+ *   CRDT_REINDEX_INVALID  def_count[s] > in Dcap: the output state is the empty state with count 0 and
+ *                         no other bit is set.
+ *   CRDT_REINDEX_VALUES   a non-empty value slot (non-zero clock row) of a kept key / of the register at
+ *                         a position >= out V: that slot is dropped.
+ * Limits (past them CRDT_EUNSUPPORTED before any launch): 1 <= V <= 64 and planes <= 64; N, Dcap, M, K
+ * and A are bounded only by 2^31 - 1 (Map and MVReg: K and A by 2^25), far past the 4,096 / 1,024
+ * actors the consuming calls take.  N == 0 returns CRDT_OK.  Device memory only.  The calls keep one
+ * flag per input index of a mapped axis in the ctx scratch (grown on the first call that needs more,
+ * as for every call); nothing else is allocated. */
+#define CRDT_REINDEX_DCAP     1u
+#define CRDT_REINDEX_DROPPED  2u
+#define CRDT_REINDEX_INVALID  4u
+#define CRDT_REINDEX_VALUES  16u
+
+int crdt_reindex_map_u32(crdt_ctx *ctx, const uint32_t *old_ids, size_t n_old, const uint32_t *new_ids, size_t n_new,
+                         uint32_t *src, uint32_t *n_lost);
+int crdt_reindex_map_u64(crdt_ctx *ctx, const uint64_t *old_ids, size_t n_old, const uint64_t *new_ids, size_t n_new,
+                         uint32_t *src, uint32_t *n_lost);
+int crdt_rows_reindex(crdt_ctx *ctx, const uint64_t *in, size_t in_stride, size_t A_in, uint64_t *out, size_t out_stride,
+                      size_t A_out, size_t planes, size_t N, const uint32_t *src, uint32_t *status);
+int crdt_bitmap_reindex(crdt_ctx *ctx, const uint64_t *in, size_t in_stride, size_t U_in, uint64_t *out, size_t out_stride,
+                        size_t U_out, size_t N, const uint32_t *src, uint32_t *status);
+int crdt_orswot_reindex(crdt_ctx *ctx, const crdt_orswot_states *in, const uint32_t *actor_src, const uint32_t *member_src,
+                        const crdt_orswot_states *out, uint32_t *status);
+int crdt_mvreg_reindex(crdt_ctx *ctx, const crdt_mvreg_states *in, const uint32_t *actor_src, const crdt_mvreg_states *out,
+                       uint32_t *status);
+int crdt_map_reindex(crdt_ctx *ctx, const crdt_map_states *in, const crdt_map_deferred *in_def, const uint32_t *actor_src,
+                     const uint32_t *key_src, const crdt_map_states *out, const crdt_map_deferred *out_def,
+                     uint32_t *status);
+
 /* ---- causal helpers on dense clock rows -----------------------------------
  * Row-pair ops over N pairs (x_i, y_i) of A-word rows (VClock, GCounter inner, or a PNCounter
  * P‖N row with A = 2·actors):

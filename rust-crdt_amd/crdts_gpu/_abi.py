@@ -26,6 +26,8 @@ CRDT_KIND = {"vclock": 1, "gcounter": 2, "pncounter": 3, "gset": 4}
 CRDT_RED_MAX, CRDT_RED_MIN, CRDT_RED_SUM = 0, 1, 2
 # crdt_*_eq_batch: the components that differ
 CRDT_NE_CLOCK, CRDT_NE_ENTRIES, CRDT_NE_VALUES, CRDT_NE_DEFERRED, CRDT_NE_INVALID = 1, 2, 4, 8, 16
+# crdt_*_reindex: the status word's bits
+CRDT_REINDEX_DCAP, CRDT_REINDEX_DROPPED, CRDT_REINDEX_INVALID, CRDT_REINDEX_VALUES = 1, 2, 4, 16
 
 # Every symbol declared in include/crdt_gpu.h (checked by tests/test_abi.py).
 EXPORTS = (
@@ -77,6 +79,8 @@ EXPORTS = (
     "crdt_vclock_ops_egress", "crdt_pncounter_ops_egress", "crdt_gset_ops_egress", "crdt_lwwreg_ops_egress",
     "crdt_mvreg_eq_batch", "crdt_orswot_eq_batch", "crdt_map_eq_batch",
     "crdt_map_counter_eq_batch", "crdt_map_orswot_eq_batch", "crdt_map_nested_eq_batch",
+    "crdt_reindex_map_u32", "crdt_reindex_map_u64", "crdt_rows_reindex", "crdt_bitmap_reindex",
+    "crdt_orswot_reindex", "crdt_mvreg_reindex", "crdt_map_reindex",
 )
 
 
@@ -496,6 +500,16 @@ _SIGS.update({  # ... of the value-typed Maps (csrc/eq_vmap.hip)
     f"crdt_map_{_n}_eq_batch": ([P, ctypes.POINTER(_st), ctypes.POINTER(MapDeferred), ctypes.POINTER(_st),
                                  ctypes.POINTER(MapDeferred), P], ctypes.c_int)
     for _n, _st in (("counter", MapCounterStates), ("orswot", MapOrswotStates), ("nested", MapNestedStates))
+})
+_SIGS.update({  # re-index of resident states (csrc/reindex.hip)
+    "crdt_reindex_map_u32": ([P, P, S, P, S, P, P], ctypes.c_int),
+    "crdt_reindex_map_u64": ([P, P, S, P, S, P, P], ctypes.c_int),
+    "crdt_rows_reindex": ([P, P, S, S, P, S, S, S, S, P, P], ctypes.c_int),
+    "crdt_bitmap_reindex": ([P, P, S, S, P, S, S, S, P, P], ctypes.c_int),
+    "crdt_orswot_reindex": ([P, ctypes.POINTER(OrswotStates), P, P, ctypes.POINTER(OrswotStates), P], ctypes.c_int),
+    "crdt_mvreg_reindex": ([P, ctypes.POINTER(MVRegStates), P, ctypes.POINTER(MVRegStates), P], ctypes.c_int),
+    "crdt_map_reindex": ([P, ctypes.POINTER(MapStates), ctypes.POINTER(MapDeferred), P, P, ctypes.POINTER(MapStates),
+                          ctypes.POINTER(MapDeferred), P], ctypes.c_int),
 })
 for _t in ("vclock", "pncounter", "gset"):
     _SIGS[f"crdt_{_t}_ops_ingest"] = ([P, P, P, S, P, S, ctypes.POINTER(DotOpsBuf), P, ctypes.POINTER(U64)], ctypes.c_int)

@@ -22,6 +22,13 @@ def merge_batch(self_states: torch.Tensor, other_states: torch.Tensor,
     return _lattice.merge_batch("gcounter", ctx, self_states, other_states)
 
 
+def reindex(rows: torch.Tensor, src: Optional[torch.Tensor], A: Optional[int] = None, ctx: Optional[Context] = None):
+    """(N, A_in) counters gathered into (N, A) columns through the axis map `src` (reindex.index_map; None
+    = the identity prefix).  Returns (rows, status): REINDEX_DROPPED where a dropped actor held a counter."""
+    from . import reindex as _rx
+    return _rx.rows(rows, src, A, ctx=ctx)
+
+
 def read(states: torch.Tensor, ctx: Optional[Context] = None) -> list:
     """GCounter::read (gcounter.rs:70-72) of every row (N, A) or of one (A,) state: the exact sum,
     as 128-bit words on the device (crdt_gcounter_read), returned as Python ints (BigUint)."""

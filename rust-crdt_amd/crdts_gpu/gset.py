@@ -66,3 +66,12 @@ def read(states: torch.Tensor, elems: Optional[torch.Tensor] = None) -> List[lis
 
 ingest = _wire.gset_ingest
 egress = _wire.gset_egress
+
+
+def reindex(rows: torch.Tensor, src: Optional[torch.Tensor], U: Optional[int] = None, ctx: Optional[Context] = None,
+            U_in: Optional[int] = None):
+    """(N, W_in) bitmap rows gathered bit by bit into a universe of `U` elements through the axis map
+    `src` (reindex.index_map; None = the identity prefix).  Returns (rows, status): REINDEX_DROPPED where
+    a dropped element was in the set."""
+    from . import reindex as _rx
+    return _rx.bitmaps(rows, src, U, ctx=ctx, bits_in=U_in)

@@ -437,6 +437,34 @@ def eq_batch(x: MapStates, y: MapStates, ctx: Optional[Context] = None) -> torch
     return ne
 
 
+def reindex(states: MapStates, actors: Optional[torch.Tensor] = None, keys: Optional[torch.Tensor] = None,
+            K: Optional[int] = None, A: Optional[int] = None, V: Optional[int] = None, Dcap: Optional[int] = None,
+            ctx: Optional[Context] = None):
+    """The states gathered into another dense layout (crdt_map_reindex): actor columns through the axis
+    map `actors`, key rows and bits through `keys` (reindex.index_map builds both; None = the identity
+    prefix), `V` value slots (slot v stays slot v) and `Dcap` deferred slots.  A missing size is the
+    map's length, or the input's.  Returns (MapStates, status): status (N,) int32 of REINDEX_DCAP /
+    REINDEX_DROPPED / REINDEX_INVALID / REINDEX_VALUES.  The input is read only; the output is new memory."""
+    from . import reindex as _rx
+    ctx = ctx or Context.default(states.clock.device.index)
+    a, ad = _map_states_structs(ctx, states, "map.reindex(states)")
+    ap, na = _rx.src_ptr(ctx, actors, "map.reindex(actors)")
+    kp, nk = _rx.src_ptr(ctx, keys, "map.reindex(keys)")
+    A2 = _rx.out_size(A, na, a.A, "map.reindex(A)")
+    K2 = _rx.out_size(K, nk, a.K, "map.reindex(K)")
+    V2 = a.V if V is None else int(V)
+    D2 = ad.Dcap if Dcap is None else int(Dcap)
+    dev, dt, N = states.clock.device, states.clock.dtype, a.N
+    e = lambda *shape: torch.empty(shape, dtype=dt, device=dev)  # noqa: E731
+    out = MapStates(e(N, A2), e(N, K2, A2), e(N, K2, V2, A2), e(N, K2, V2), e(N, D2, A2), e(N, D2, (K2 + 63) // 64),
+                    torch.empty(N, dtype=torch.int32, device=dev))
+    b, bd = _map_states_structs(ctx, out, "map.reindex(out)")
+    status = torch.empty(N, dtype=torch.int32, device=dev)
+    ctx.call("crdt_map_reindex", ctypes.byref(a), ctypes.byref(ad), ap, kp, ctypes.byref(b), ctypes.byref(bd),
+             status.data_ptr())
+    return out, status
+
+
 # ---- Map<K, GCounter> / Map<K, PNCounter> (crdt_map_counter_lub_many, round 4) ----------------------
 class MapCounterLub(NamedTuple):
     clock: torch.Tensor               # (G, A)

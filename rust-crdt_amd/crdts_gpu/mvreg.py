@@ -123,6 +123,26 @@ def eq_batch(x_vclk: torch.Tensor, x_vval: torch.Tensor, y_vclk: torch.Tensor, y
     return ne
 
 
+def reindex(vclk: torch.Tensor, vval: torch.Tensor, actors: Optional[torch.Tensor] = None, A: Optional[int] = None,
+            V: Optional[int] = None, ctx: Optional[Context] = None):
+    """The (N, V, A) / (N, V) registers gathered into another dense layout (crdt_mvreg_reindex): actor
+    columns through the axis map `actors` (reindex.index_map builds it; None = the identity prefix),
+    `V` value slots (slot v stays slot v, holes included).  A missing size is the map's length, or the
+    input's.  Returns ((vclk, vval), status): status (N,) int32 of REINDEX_DROPPED / REINDEX_VALUES."""
+    from . import reindex as _rx
+    ctx = ctx or Context.default(vclk.device.index)
+    a = _states(ctx, vclk, vval, "mvreg.reindex(in)")
+    ap, na = _rx.src_ptr(ctx, actors, "mvreg.reindex(actors)")
+    A2 = _rx.out_size(A, na, a.A, "mvreg.reindex(A)")
+    V2 = a.V if V is None else int(V)
+    out_c = torch.empty((a.N, V2, A2), dtype=vclk.dtype, device=vclk.device)
+    out_v = torch.empty((a.N, V2), dtype=vval.dtype, device=vclk.device)
+    b = _states(ctx, out_c, out_v, "mvreg.reindex(out)")
+    status = torch.empty(a.N, dtype=torch.int32, device=vclk.device)
+    ctx.call("crdt_mvreg_reindex", ctypes.byref(a), ap, ctypes.byref(b), status.data_ptr())
+    return (out_c, out_v), status
+
+
 class MVRegOpBatch(NamedTuple):
     op_off: torch.Tensor    # (N+1,) int64
     clk_row: torch.Tensor   # (n_ops,) int32

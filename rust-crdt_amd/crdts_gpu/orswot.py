@@ -415,6 +415,33 @@ def eq_batch(x: OrswotStates, y: OrswotStates, ctx: Optional[Context] = None) ->
     return ne
 
 
+def reindex(states: OrswotStates, actors: Optional[torch.Tensor] = None, members: Optional[torch.Tensor] = None,
+            M: Optional[int] = None, A: Optional[int] = None, Dcap: Optional[int] = None,
+            ctx: Optional[Context] = None):
+    """The states gathered into another dense layout (crdt_orswot_reindex): actor columns through the
+    axis map `actors`, member rows and bits through `members` (reindex.index_map builds both; None =
+    the identity prefix), `Dcap` deferred slots.  A missing size is the map's length, or the input's.
+    Returns (OrswotStates, status): status (N,) int32 of REINDEX_DCAP / REINDEX_DROPPED /
+    REINDEX_INVALID.  The input is read only; the output is new memory."""
+    from . import reindex as _rx
+    ctx = ctx or Context.default(states.clock.device.index)
+    a = _states_struct(ctx, states, "orswot.reindex(states)")
+    ap, na = _rx.src_ptr(ctx, actors, "orswot.reindex(actors)")
+    mp, nm = _rx.src_ptr(ctx, members, "orswot.reindex(members)")
+    A2 = _rx.out_size(A, na, a.A, "orswot.reindex(A)")
+    M2 = _rx.out_size(M, nm, a.M, "orswot.reindex(M)")
+    D2 = a.Dcap if Dcap is None else int(Dcap)
+    dev, dt, N = states.clock.device, states.clock.dtype, a.N
+    out = OrswotStates(torch.empty((N, A2), dtype=dt, device=dev), torch.empty((N, M2, A2), dtype=dt, device=dev),
+                       torch.empty((N, D2, A2), dtype=dt, device=dev),
+                       torch.empty((N, D2, (M2 + 63) // 64), dtype=dt, device=dev),
+                       torch.empty(N, dtype=torch.int32, device=dev))
+    b = _states_struct(ctx, out, "orswot.reindex(out)")
+    status = torch.empty(N, dtype=torch.int32, device=dev)
+    ctx.call("crdt_orswot_reindex", ctypes.byref(a), ap, mp, ctypes.byref(b), dptr(status))
+    return out, status
+
+
 # ---------------------------------------------------------------------------------------------
 # Batched reads: Orswot::read / contains (orswot.rs:253-279) as ReadCtx (readctx.py)
 # ---------------------------------------------------------------------------------------------

@@ -28,6 +28,14 @@ def merge_batch(self_states: torch.Tensor, other_states: torch.Tensor,
     return _lattice.merge_batch("pncounter", ctx, self_states, other_states, width_div=2)
 
 
+def reindex(rows: torch.Tensor, src: Optional[torch.Tensor], A: Optional[int] = None, ctx: Optional[Context] = None):
+    """(N, 2 A_in) rows P ‖ N gathered into (N, 2 A): both halves through the same axis map `src`
+    (reindex.index_map; None = the identity prefix).  Returns (rows, status): REINDEX_DROPPED where a
+    dropped actor held a counter."""
+    from . import reindex as _rx
+    return _rx.rows(rows, src, A, planes=2, ctx=ctx)
+
+
 def read(states: torch.Tensor, ctx: Optional[Context] = None) -> list:
     """PNCounter::read (pncounter.rs:110-115) of every row (N, 2A) = P ‖ N or of one (2A,) state:
     exact P - N as 128-bit two's complement on the device (crdt_pncounter_read), returned as

@@ -87,6 +87,13 @@ ingest = _wire.vclock_ingest
 egress = _wire.vclock_egress
 
 
+def reindex(rows: torch.Tensor, src: Optional[torch.Tensor], A: Optional[int] = None, ctx: Optional[Context] = None):
+    """(N, A_in) clocks gathered into (N, A) columns through the axis map `src` (reindex.index_map; None
+    = the identity prefix).  Returns (rows, status): REINDEX_DROPPED where a dropped actor held a counter."""
+    from . import reindex as _rx
+    return _rx.rows(rows, src, A, ctx=ctx)
+
+
 # ---- reference-shaped clocks <-> dense rows, and the per-clock accessors ----------------------------
 def from_clocks(clocks: Sequence[Mapping[Hashable, int]], actors: Optional[Index] = None, width: int = 0,
                 device=None) -> Tuple[torch.Tensor, Index]:

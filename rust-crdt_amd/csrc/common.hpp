@@ -130,6 +130,8 @@ struct Tune {
   int read_nt = 1;             // ... non-temporal loads (the entries are read once)
   int eqv_ppl = 8;             // value-typed Map equality, per-key kernel: 16-byte pieces per lane of a key's segment
   int eqv_bpc = 32;            // ... workgroups per CU of its grid-stride loop (and of the register kernel's)
+  int rx_lds = 1;              // reindex with a column map: input rows staged in LDS by 16-byte loads (0: the
+                               //     output lanes gather 8-byte words straight from memory)
 };
 
 struct PendingTiming {

@@ -268,6 +268,7 @@ static void apply_tune(crdt_ctx *ctx, const char *t) {
       else if (k == "mvfbpc" && v >= 1 && v <= 64) ctx->tune.mvreg_forget_bpc = v;
       else if (k == "eqvppl" && v >= 1 && v <= 64) ctx->tune.eqv_ppl = v;
       else if (k == "eqvbpc" && v >= 1 && v <= 4096) ctx->tune.eqv_bpc = v;
+      else if (k == "rxlds" && v >= 0 && v <= 1) ctx->tune.rx_lds = v;
     }
     pos = end + 1;
   }
