@@ -37,6 +37,12 @@ constexpr int kWave = 64;
 #endif
 constexpr int kBlock = 256;
 
+// Lane i's word to the whole wave (i uniform): v_readlane, no LDS round trip.
+__device__ __forceinline__ unsigned rl32(unsigned x, int i) { return (unsigned)__builtin_amdgcn_readlane((int)x, i); }
+__device__ __forceinline__ u64 rl64(u64 x, int i) {
+  return ((u64)rl32((unsigned)(x >> 32), i) << 32) | rl32((unsigned)x, i);
+}
+
 struct KernelTimer {
   double total_ms = 0.0;
   uint64_t launches = 0;

@@ -22,7 +22,7 @@
 // of every row; the outer deferred removes in LDS for the whole stream.  Every global word is read
 // back only by the lane that wrote it (row words by the lane of their actor), or is a scalar every
 // lane writes with the same value (nval, ivv, id_n, id_keys).
-#include "common.hpp"
+#include "vmap_apply_frame.hpp"
 
 namespace crdt {
 
@@ -51,15 +51,11 @@ struct NestedApplyPlan {
   unsigned long long n_keys, n_ops;
   unsigned *status;
   unsigned wpb;
-  u64 *resume = nullptr;  // [N] (Dcap > Dl): op offset where a state continues in pass 2, or kMnaDone
+  u64 *resume = nullptr;  // [N] (Dcap > Dl): op offset where a state continues in pass 2, or kVmapDone
   const u64 *y;  // forget
   unsigned long long y_stride;
 };
-constexpr u64 kMnaDone = ~0ull;
 
-// The rows of outer key k of state s, and the inner-Map operations on them.
-// op headers batched 64 at a time into lanes and read by v_readlane (build option; 0 = one global
-// read of each field per op)
 // waves per SIMD asked of the register allocator for A <= 128 (build option).  4 = the round-5 kernel's
 // natural 127 VGPRs; the round-6 pass structure needs 131 unforced, which is 3 waves per SIMD and ran
 // 25% slower (2.09 vs 1.67 ms, profiles/r06_apply_ab.log).  0 = the compiler's choice.
@@ -71,14 +67,8 @@ constexpr u64 kMnaDone = ~0ull;
 #else
 #define MNA_WPE_ATTR
 #endif
-#ifndef CRDT_MNA_HDR
-#define CRDT_MNA_HDR 1
-#endif
-__device__ __forceinline__ unsigned rl32(unsigned x, int i) { return (unsigned)__builtin_amdgcn_readlane((int)x, i); }
-__device__ __forceinline__ u64 rl64(u64 x, int i) {
-  return ((u64)rl32((unsigned)(x >> 32), i) << 32) | rl32((unsigned)x, i);
-}
 
+// The rows of outer key k of state s, and the inner-Map operations on them.
 constexpr int kNaKw = 4;  // inner-key mask words at most (K2 <= 256)
 
 // KW: mask words per key set at compile time, 1 (K2 <= 64: the round-5 code) or kNaKw (kw of them live)
@@ -392,11 +382,9 @@ __device__ __forceinline__ NaKey<APL, KW> na_key(const NestedApplyPlan &p, unsig
                     (unsigned)p.Id, (unsigned)p.Vs};
 }
 
-// TIER false: every state, the Map's deferred list in the Dl LDS slots only; a state whose list
-// needs slot Dl (Dcap > Dl) stores itself and records the op to continue from (resume[s]).  TIER
-// true: those states alone, slots past Dl used in place in the caller's slot arrays.  (One body with
-// the branch compiles the slot accesses to flat instructions and slows every state; see
-// csrc/map_counter_apply.hip.)
+// What PASS means, the outer deferred slots (sl) and apply_deferred are csrc/vmap_apply_frame.hpp's.
+// The prologue, the Map-level Rm and the epilogue below are the same text in the three value-typed
+// apply kernels: as shared functions they cost registers (see the header).
 template <int APL, int PASS, int KW>
 __global__ __launch_bounds__(256) MNA_WPE_ATTR void map_nested_apply_kernel(NestedApplyPlan p) {
   extern __shared__ u64 lds[];
@@ -405,7 +393,7 @@ __global__ __launch_bounds__(256) MNA_WPE_ATTR void map_nested_apply_kernel(Nest
   if (wv >= (int)p.wpb || s >= p.N) return;  // (whole waves)
   constexpr bool TIER = PASS == 2;
   if constexpr (TIER) {
-    if (p.resume[s] == kMnaDone) return;
+    if (p.resume[s] == kVmapDone) return;
   }
   const unsigned long long A = p.A, K = p.K, K2 = p.K2, Kw = p.Kw, Dcap = p.Dcap, Dl = p.Dl;
   // The outer deferred removes: slots d < Dl in LDS, slots Dl <= d < Dcap in the caller's own slot
@@ -413,29 +401,13 @@ __global__ __launch_bounds__(256) MNA_WPE_ATTR void map_nested_apply_kernel(Nest
   u64 *sclk = lds + (unsigned long long)wv * Dl * (A + Kw);  // [Dl][A] the outer rm clocks
   u64 *skey = sclk + Dl * A;                                 // [Dl][Kw] their key bitmaps
   u64 *gclk = p.def_clock + s * Dcap * A, *gkey = p.def_keys + s * Dcap * Kw;
-  // (d is wave-uniform; the pass-1 body never reaches d >= Dl)
-  auto clk = [&](unsigned d, unsigned long long a) -> u64 {
-    if (TIER && d >= Dl) return gclk[d * A + a];
-    return sclk[d * A + a];
-  };
-  auto set_clk = [&](unsigned d, unsigned long long a, u64 v) {
-    if (TIER && d >= Dl) gclk[d * A + a] = v;
-    else sclk[d * A + a] = v;
-  };
-  auto key = [&](unsigned d, unsigned long long w) -> u64 {
-    if (TIER && d >= Dl) return gkey[d * Kw + w];
-    return skey[d * Kw + w];
-  };
-  auto set_key = [&](unsigned d, unsigned long long w, u64 v) {
-    if (TIER && d >= Dl) gkey[d * Kw + w] = v;
-    else skey[d * Kw + w] = v;
-  };
+  const VmapSlots<TIER> sl{sclk, skey, gclk, gkey, A, Kw, Dl, lane};
   const unsigned long long ob = p.op_off[s], oe = p.op_off[s + 1];
   unsigned dcnt = p.def_count[s];
   if (dcnt > Dcap || oe < ob || oe > p.n_ops) {
     if (lane == 0) {
       p.status[s] = (dcnt > Dcap ? 4u : 0u) | (oe < ob || oe > p.n_ops ? 8u : 0u);
-      if (PASS == 1) p.resume[s] = kMnaDone;
+      if (PASS == 1) p.resume[s] = kVmapDone;
     }
     return;  // state left untouched
   }
@@ -458,47 +430,21 @@ __global__ __launch_bounds__(256) MNA_WPE_ATTR void map_nested_apply_kernel(Nest
   u64 c[APL];
 #pragma unroll
   for (int j = 0; j < APL; ++j) c[j] = word(j) < A ? C[word(j)] : 0ull;
-  for (unsigned d = 0; d < dcnt && d < Dl; ++d) {
-    for (unsigned long long a = (unsigned long long)lane; a < A; a += kWave) sclk[d * A + a] = gclk[d * A + a];
-    for (unsigned long long w = (unsigned long long)lane; w < Kw; w += kWave) skey[d * Kw + w] = gkey[d * Kw + w];
-  }
-  // apply_deferred (map.rs:311-316): full on its first run, then restricted to the Up's own key (the
-  // only rows an Up changes; forgets are idempotent and commute — see csrc/map_counter_apply.hip)
+  sl.stage_in(dcnt);
   bool full = true;
-  auto map_apply_deferred = [&](unsigned long long kk) {
-    unsigned o = 0;
-    for (unsigned d = 0; d < dcnt; ++d) {
-      u64 r[APL];
-#pragma unroll
-      for (int j = 0; j < APL; ++j) r[j] = word(j) < A ? clk(d, word(j)) : 0ull;
-      for (unsigned long long w = full ? 0 : kk / 64; w < (full ? Kw : kk / 64 + 1); ++w) {
-        u64 bits = key(d, w) & (full ? ~0ull : 1ull << (kk % 64));
-        while (bits) {
-          const unsigned long long k = w * 64 + (unsigned long long)__builtin_ctzll(bits);
-          bits &= bits - 1;
-          if (k < K) {
-            const NaKey<APL, KW> q = na_key<APL, KW>(p, s, k, lane);
-            q.key_rm(r);
-            st |= q.stb;
-          }
-        }
-      }
-      if (NaKey<APL, KW>::leq(r, c)) continue;  // no longer deferred
-      if (o != d) {
-        for (unsigned long long a = (unsigned long long)lane; a < A; a += kWave) set_clk(o, a, clk(d, a));
-        for (unsigned long long w = (unsigned long long)lane; w < Kw; w += kWave) set_key(o, w, key(d, w));
-      }
-      ++o;
-    }
-    dcnt = o;
-    full = false;
+  auto key_rm = [&](unsigned long long k, const u64 (&r)[APL]) {
+    const NaKey<APL, KW> q = na_key<APL, KW>(p, s, k, lane);
+    q.key_rm(r);
+    st |= q.stb;
   };
-
-  // Op headers in batches of 64 (CRDT_MNA_HDR): lane i loads op o0 + i's fields (coalesced, all in
-  // flight together) and op o's fields reach the wave by v_readlane, not by a global round trip per op.
+  // (a lambda, not a direct call: with the call inlined at the Up the inliner keeps other NaKey
+  // members out of line in the KW 4 instances, which then need more scratch and lose a wave per SIMD)
+  auto map_apply_deferred = [&](unsigned long long kk) { vmap_apply_deferred<APL, TIER>(sl, dcnt, full, c, K, kk, key_rm); };
+  // Op headers in batches of 64: lane i loads op o0 + i's fields (coalesced, all in flight
+  // together) and op o's fields reach the wave by v_readlane, not by a global round trip per op.
   for (unsigned long long o0 = start; o0 < oe; o0 += kWave) {
     const unsigned long long mo = o0 + (unsigned long long)lane;
-    const bool hin = CRDT_MNA_HDR && mo < oe;
+    const bool hin = mo < oe;
     const unsigned h_kind = hin ? p.kind[mo] : 0u, h_ik = hin ? p.ikind[mo] : 0u, h_a = hin ? p.actor[mo] : 0u;
     const unsigned h_k = hin ? p.key[mo] : 0u, h_ia = hin ? p.iactor[mo] : 0u, h_jk = hin ? p.ikey[mo] : 0u;
     const unsigned h_rr = hin ? p.clk_row[mo] : 0u;
@@ -507,19 +453,19 @@ __global__ __launch_bounds__(256) MNA_WPE_ATTR void map_nested_apply_kernel(Nest
     const int nb = (int)(oe - o0 < (unsigned long long)kWave ? oe - o0 : (unsigned long long)kWave);
   for (int hi = 0; hi < nb; ++hi) {
     const unsigned long long o = o0 + (unsigned long long)hi;
-    const unsigned kind = CRDT_MNA_HDR ? rl32(h_kind, hi) : p.kind[o];
+    const unsigned kind = rl32(h_kind, hi);
     if (kind == 0) {  // ---- Op::Up { dot, key, op: an inner Map op }
-      const unsigned a = CRDT_MNA_HDR ? rl32(h_a, hi) : p.actor[o], ik = CRDT_MNA_HDR ? rl32(h_ik, hi) : p.ikind[o];
-      const unsigned long long k = CRDT_MNA_HDR ? rl32(h_k, hi) : p.key[o];
-      const u64 cnt = CRDT_MNA_HDR ? rl64(h_c, hi) : p.counter[o];
-      const unsigned rr = CRDT_MNA_HDR ? rl32(h_rr, hi) : p.clk_row[o];
-      const unsigned ia = ik == 0 ? (CRDT_MNA_HDR ? rl32(h_ia, hi) : p.iactor[o]) : 0u;
-      const unsigned long long jk = ik == 0 ? (CRDT_MNA_HDR ? rl32(h_jk, hi) : p.ikey[o]) : 0ull;
+      const unsigned a = rl32(h_a, hi), ik = rl32(h_ik, hi);
+      const unsigned long long k = rl32(h_k, hi);
+      const u64 cnt = rl64(h_c, hi);
+      const unsigned rr = rl32(h_rr, hi);
+      const unsigned ia = ik == 0 ? rl32(h_ia, hi) : 0u;
+      const unsigned long long jk = ik == 0 ? rl32(h_jk, hi) : 0ull;
       // an inner Rm's key set: K2w words of ikeys [n_ops][K2w] (one word batched with the headers);
       // read here for the range check and again at the Rm, so no word is held across the key's setup
       const auto ibw = [&](int x) -> u64 {
         return ik != 1 || (unsigned long long)x >= p.K2w ? 0ull
-               : p.K2w == 1 ? (CRDT_MNA_HDR ? rl64(h_ib, hi) : p.ikeys[o])
+               : p.K2w == 1 ? rl64(h_ib, hi)
                             : p.ikeys[o * p.K2w + x];
       };
       bool kbad = false;  // a key bit past K2
@@ -538,7 +484,7 @@ __global__ __launch_bounds__(256) MNA_WPE_ATTR void map_nested_apply_kernel(Nest
       q.bump(q.ec, a, cnt);  // entry.clock.apply(dot) (an absent entry: its rows are Map::default())
       u64 r[APL];
       q.ld(p.clk_pool + (unsigned long long)rr * A, r);
-      if (ik == 0) q.inner_up(ia, CRDT_MNA_HDR ? rl64(h_ic, hi) : p.icounter[o], jk, r, CRDT_MNA_HDR ? rl64(h_v, hi) : p.val[o]);
+      if (ik == 0) q.inner_up(ia, rl64(h_ic, hi), jk, r, rl64(h_v, hi));
       else {
         u64 ib[KW];
 #pragma unroll
@@ -551,8 +497,8 @@ __global__ __launch_bounds__(256) MNA_WPE_ATTR void map_nested_apply_kernel(Nest
         if ((unsigned)j == a / 64 && (unsigned long long)lane == a % 64 && c[j] < cnt) c[j] = cnt;
       map_apply_deferred(k);
     } else if (kind == 1) {  // ---- Op::Rm -> apply_keyset_rm
-      const unsigned rr = CRDT_MNA_HDR ? rl32(h_rr, hi) : p.clk_row[o];
-      const u64 kb = CRDT_MNA_HDR ? rl64(h_kb, hi) : p.key_off[o], ke = CRDT_MNA_HDR ? rl64(h_ke, hi) : p.key_off[o + 1];
+      const unsigned rr = rl32(h_rr, hi);
+      const u64 kb = rl64(h_kb, hi), ke = rl64(h_ke, hi);
       if (rr >= p.n_clk_rows || ke < kb || ke > p.n_keys) {
         st |= 2u;
         continue;
@@ -575,7 +521,7 @@ __global__ __launch_bounds__(256) MNA_WPE_ATTR void map_nested_apply_kernel(Nest
       for (unsigned d = 0; d < dcnt && slot < 0; ++d) {
         bool ne = false;
 #pragma unroll
-        for (int j = 0; j < APL; ++j) ne = ne || (word(j) < A && clk(d, word(j)) != r[j]);
+        for (int j = 0; j < APL; ++j) ne = ne || (word(j) < A && sl.clk(d, word(j)) != r[j]);
         if (!__ballot(ne)) slot = (int)d;
       }
       if (slot < 0) {
@@ -593,12 +539,12 @@ __global__ __launch_bounds__(256) MNA_WPE_ATTR void map_nested_apply_kernel(Nest
         if (TIER) peak = dcnt > peak ? dcnt : peak;  // (pass 1: never past the input count's slots in memory)
 #pragma unroll
         for (int j = 0; j < APL; ++j)
-          if (word(j) < A) set_clk(slot, word(j), r[j]);
-        for (unsigned long long w = (unsigned long long)lane; w < Kw; w += kWave) set_key(slot, w, 0);
+          if (word(j) < A) sl.set_clk(slot, word(j), r[j]);
+        for (unsigned long long w = (unsigned long long)lane; w < Kw; w += kWave) sl.set_key(slot, w, 0);
       }
       for (u64 i = kb; i < ke; ++i) {
         const unsigned long long k = p.keys[i];
-        if (k < K && (unsigned long long)lane == (k / 64) % kWave) set_key(slot, k / 64, key(slot, k / 64) | 1ull << (k % 64));
+        if (k < K && (unsigned long long)lane == (k / 64) % kWave) sl.set_key(slot, k / 64, sl.key(slot, k / 64) | 1ull << (k % 64));
       }
     } else {
       st |= 2u;
@@ -609,21 +555,15 @@ done:
 #pragma unroll
   for (int j = 0; j < APL; ++j)
     if (word(j) < A) C[word(j)] = c[j];
-  for (unsigned d = 0; d < dcnt && d < Dl; ++d) {  // (slots past Dl are already in place)
-    for (unsigned long long a = (unsigned long long)lane; a < A; a += kWave) gclk[d * A + a] = sclk[d * A + a];
-    for (unsigned long long w = (unsigned long long)lane; w < Kw; w += kWave) gkey[d * Kw + w] = skey[d * Kw + w];
-  }
+  sl.write_back(dcnt);
   // slots the deferred list vacated, zeroed as a fresh state's: pass 1 wrote none past its final count
   // to memory, so only the input's [dcnt, def_count[s]) can be stale there; pass 2 tracks its peak
   const unsigned hi = TIER ? peak : p.def_count[s];
-  for (unsigned d = dcnt; d < hi; ++d) {
-    for (unsigned long long a = (unsigned long long)lane; a < A; a += kWave) gclk[d * A + a] = 0ull;
-    for (unsigned long long w = (unsigned long long)lane; w < Kw; w += kWave) gkey[d * Kw + w] = 0ull;
-  }
+  sl.zero(dcnt, hi);
   if (lane == 0) {
     p.def_count[s] = dcnt;
     p.status[s] = st;
-    if (PASS == 1) p.resume[s] = resume_at == 0xffffffffu ? kMnaDone : resume_at;
+    if (PASS == 1) p.resume[s] = resume_at == 0xffffffffu ? kVmapDone : resume_at;
   }
 }
 
@@ -694,79 +634,15 @@ extern "C" int crdt_map_nested_apply_batch(crdt_ctx *ctx, const crdt_map_nested_
                      !ops->icounter || !ops->ikey || !ops->val || !ops->ikeys || !ops->clk_row))
     return fail(ctx, CRDT_EINVAL, "map_nested_apply_batch: NULL op buffer");
   NestedApplyPlan p = nested_plan(m);
-  // outer deferred slots in LDS: up to 16 (the rest of Dcap in the caller's slot arrays), fewer where a
-  // slot is wide (at most 8,192 words per wave)
-  const size_t Dl = std::min<size_t>(Dcap, std::min<size_t>(16, 8192 / (A + p.Kw)));
-  const size_t per_wave = Dl * (A + p.Kw) * 8;
-  unsigned wpb = 4;
-  while (wpb > 1 && per_wave * wpb > 64 * 1024) --wpb;
-  CRDT_HIP(ctx, hipSetDevice(ctx->device));
-  p.Dcap = Dcap;
-  p.Dl = Dl;
-  p.def_clock = (u64 *)def_clock;
-  p.def_keys = (u64 *)def_keys;
-  p.def_count = def_count;
-  p.op_off = (const u64 *)ops->op_off;
-  p.kind = ops->kind;
-  p.ikind = ops->ikind;
-  p.actor = ops->actor;
-  p.key = ops->key;
-  p.iactor = ops->iactor;
-  p.ikey = ops->ikey;
-  p.counter = (const u64 *)ops->counter;
-  p.icounter = (const u64 *)ops->icounter;
-  p.val = (const u64 *)ops->val;
-  p.ikeys = (const u64 *)ops->ikeys;
-  p.clk_row = ops->clk_row;
-  p.clk_pool = (const u64 *)ops->clk_pool;
-  p.n_clk_rows = ops->clk_pool ? ops->n_clk_rows : 0;
-  p.key_off = (const u64 *)ops->key_off;
-  p.keys = ops->keys;
-  p.n_keys = ops->keys ? ops->n_keys : 0;
-  p.n_ops = ops->n_ops;
-  p.status = status;
-  p.wpb = wpb;
-  // scratch: [resume: N words when Dcap > Dl][zero key_off: n_ops + 1 words when there is none]
-  const size_t kz = ops->key_off ? 0 : (ops->n_ops + 1) * 8, rz = Dcap > Dl ? N * 8 : 0;
-  if (kz + rz) {
-    if (int rc = ensure_scratch(ctx, kz + rz)) return rc;
-    char *sc = static_cast<char *>(ctx->scratch);
-    if (rz) p.resume = reinterpret_cast<u64 *>(sc);
-    if (kz) {  // (no Map-level Rm: every key range empty)
-      if (int rc = device_fill(ctx, sc + rz, kz, 0)) return rc;
-      p.key_off = reinterpret_cast<const u64 *>(sc + rz);
-    }
-  }
-  if (Dcap > Dl && ops->n_ops >= 0xffffffffull)  // (pass 2 resumes at a 32-bit op offset)
-    return fail(ctx, CRDT_EUNSUPPORTED, "map_nested_apply_batch: 2^32 or more ops with Dcap past the LDS slots");
-  const dim3 grid((unsigned)((N + wpb - 1) / wpb)), block(wpb * kWave);
-  const size_t lds = per_wave * wpb;
-  timing_begin(ctx, "map_nested_apply");
-  auto go_kw = [&](auto t, auto w, dim3 g, dim3 b, size_t l) {
-    constexpr int T = decltype(t)::value, W = decltype(w)::value;
-    if (A <= 64) hipLaunchKernelGGL((map_nested_apply_kernel<1, T, W>), g, b, l, ctx->stream, p);
-    else if (A <= 128) hipLaunchKernelGGL((map_nested_apply_kernel<2, T, W>), g, b, l, ctx->stream, p);
-    else if (A <= 256) hipLaunchKernelGGL((map_nested_apply_kernel<4, T, W>), g, b, l, ctx->stream, p);
-    else hipLaunchKernelGGL((map_nested_apply_kernel<8, T, W>), g, b, l, ctx->stream, p);
-  };
-  auto go = [&](auto t, dim3 g, dim3 b, size_t l) {  // (one mask word per key set up to K2 = 64)
-    if (p.K2w == 1) go_kw(t, std::integral_constant<int, 1>{}, g, b, l);
-    else go_kw(t, std::integral_constant<int, kNaKw>{}, g, b, l);
-  };
-  if (Dcap <= Dl) {
-    go(std::integral_constant<int, 0>{}, grid, block, lds);  // one pass: the whole list fits the LDS slots
-  } else {
-    go(std::integral_constant<int, 1>{}, grid, block, lds);
-    // pass 2: the few states pass 1 handed on (the rest exit at once), one wave per workgroup with the
-    // whole wave-LDS budget as slots (up to 64 KiB), so a long list mostly stays out of global memory
-    const size_t Dl2 = std::min<size_t>(Dcap, 8192 / (A + p.Kw));
-    p.Dl = Dl2;
-    p.wpb = 1;
-    go(std::integral_constant<int, 2>{}, dim3((unsigned)N), dim3(kWave), Dl2 * (A + p.Kw) * 8);
-  }
-  timing_end(ctx);
-  CRDT_HIP(ctx, hipGetLastError());
-  return CRDT_OK;
+  vmap_plan_fill(p, N, p.K, A, p.Kw, Dcap, def_clock, def_keys, def_count, *ops, status);
+  p.ikind = ops->ikind, p.iactor = ops->iactor, p.ikey = ops->ikey;
+  p.icounter = (const u64 *)ops->icounter, p.val = (const u64 *)ops->val, p.ikeys = (const u64 *)ops->ikeys;
+  return vmap_apply_run(ctx, p, 0, "map_nested_apply", [&](auto apl, auto pass, dim3 g, dim3 b, size_t l) {
+    constexpr int APL = decltype(apl)::value, T = decltype(pass)::value;
+    // (one mask word per key set up to K2 = 64)
+    if (p.K2w == 1) hipLaunchKernelGGL((map_nested_apply_kernel<APL, T, 1>), g, b, l, ctx->stream, p);
+    else hipLaunchKernelGGL((map_nested_apply_kernel<APL, T, kNaKw>), g, b, l, ctx->stream, p);
+  });
 }
 
 extern "C" int crdt_map_nested_forget_batch(crdt_ctx *ctx, const crdt_map_nested_states *m, const uint64_t *y,

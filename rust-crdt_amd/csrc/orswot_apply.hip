@@ -56,15 +56,6 @@ struct OrswotApplyPlan {
   int l2pf;   // 1: touch a one-member Rm's entry row with the batch header (CRDT_TUNE oal2=1)
 };
 
-__device__ __forceinline__ u64 rl64(u64 x, int l) {
-  const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)x, l);
-  const unsigned hi = __builtin_amdgcn_readlane((int)(unsigned)(x >> 32), l);
-  return ((u64)hi << 32) | lo;
-}
-__device__ __forceinline__ unsigned rl32(unsigned x, int l) {
-  return (unsigned)__builtin_amdgcn_readlane((int)x, l);
-}
-
 __device__ __forceinline__ void wave_fence() {
   // Stores of this wave (global and LDS) are complete and visible to its later loads (all lanes of
   // a workgroup share the CU's L1, so workgroup scope is enough).

@@ -202,12 +202,15 @@ def _future_rm_streams(rng, maps, K, A, W, T, p_rm=0.55):
     return streams, oracle_ops
 
 
+@pytest.mark.parametrize("A", [5, 70, 512])
 @pytest.mark.parametrize("W", [1, 2])
-def test_map_counter_apply_long_deferred_list(gpu_ctx, W):
+def test_map_counter_apply_long_deferred_list(gpu_ctx, W, A):
     """More deferred removes than the 16 slots the kernel holds in LDS (round 6: slots 16 .. Dcap-1 are
     used in place in the caller's slot arrays): with Dcap = 48 every state ends with 20+ removes and
-    status 0, equal to the oracle's Map.apply; Dcap = 16 on the same streams flags bit 0."""
-    N, K, A, T = 10, 6, 5, 64
+    status 0, equal to the oracle's Map.apply; Dcap = 16 on the same streams flags bit 0.  A = 70 runs
+    the two-words-per-lane instances (lanes past A masked); at A = 512 only 15 slots fit the wave's LDS
+    in either pass, so the slots from 15 up are used in place."""
+    N, K, T = 10, 6, 64
     maps = O.map_counter_objects(N, K, A, W, seed=44, steps=120)
     d = O.map_counter_to_dense(maps, K, A, W)
     rng = np.random.default_rng(7 + W)

@@ -349,15 +349,9 @@ def test_map_nested_apply_unapplied_input_deferred(gpu_ctx):
     assert len(keep) >= 8
 
 
-def test_map_nested_apply_long_outer_deferred_list(gpu_ctx):
-    """More outer deferred removes than the 16 slots the kernel holds in LDS (round 6: the rest of Dcap
-    used in place in the caller's slot arrays): outer Rms from the far future on actor 0 (Ups on actors
-    1..), 20+ removes per state at Dcap = 48, equal to the oracle's Map.apply."""
-    K, K2, A, T, Dcap = 4, 5, 4, 60, 48
-    maps = [m for m in O.nested_map_objects(14, K, K2, A, seed=85, steps=150, p_irm=0.4, p_ooo=0.5, p_rm=0.2)
-            if _fits(m)][:10]
-    N = len(maps)
-    rng = np.random.default_rng(19)
+def _future_rm_streams(rng, maps, K, K2, A, T):
+    """Streams whose outer Rms carry clocks far ahead on actor 0 (distinct per op) while the Ups use
+    actors 1.. only: no Rm is ever dominated, so every one stays deferred (a long deferred list)."""
     streams, oops = [], []
     for m in maps:
         clk = {a: m.clock.get(a) for a in range(A)}
@@ -378,6 +372,21 @@ def test_map_nested_apply_long_outer_deferred_list(gpu_ctx):
                 oo.append(MapUp(Dot(a, c), k, MapUp(Dot(ia, icn), j, MVRegPut(VClock({}), val))))
         streams.append(ops)
         oops.append(oo)
+    return streams, oops
+
+
+@pytest.mark.parametrize("A", [4, 70, 512])
+def test_map_nested_apply_long_outer_deferred_list(gpu_ctx, A):
+    """More outer deferred removes than the 16 slots the kernel holds in LDS (round 6: the rest of Dcap
+    used in place in the caller's slot arrays): outer Rms from the far future on actor 0 (Ups on actors
+    1..), 20+ removes per state at Dcap = 48, equal to the oracle's Map.apply.  A = 70 runs the
+    two-words-per-lane instances (lanes past A masked); at A = 512 only 15 slots fit the wave's LDS in
+    either pass, so the slots from 15 up are used in place."""
+    K, K2, T, Dcap = 4, 5, 60, 48
+    maps = [m for m in O.nested_map_objects(14, K, K2, A, seed=85, steps=150, p_irm=0.4, p_ooo=0.5, p_rm=0.2)
+            if _fits(m)][:10]
+    N = len(maps)
+    streams, oops = _future_rm_streams(np.random.default_rng(19), maps, K, K2, A, T)
     exps = [m.copy() for m in maps]
     for n in range(N):
         for op in oops[n]:
@@ -392,3 +401,28 @@ def test_map_nested_apply_long_outer_deferred_list(gpu_ctx):
         assert canon(got) == canon(exp), n
         longest = max(longest, len(exp.deferred))
     assert N >= 8 and 20 <= longest <= Dcap
+
+
+def test_map_nested_apply_vacated_slots_zeroed(gpu_ctx):
+    """An outer deferred list that grows past the 16 LDS slots and then empties (last Ups on actors 1
+    and 0 from past every remove's clock dominate them all): count 0, every slot written back zero,
+    state equal to the oracle's Map.apply."""
+    N, K, K2, A, T, Dcap = 6, 6, 5, 5, 64, 48
+    maps = O.nested_map_objects(N, K, K2, A, seed=86, steps=0)
+    streams, oops = _future_rm_streams(np.random.default_rng(23), maps, K, K2, A, T)
+    for s, oo in zip(streams, oops):
+        for a in (1, 0):  # (the removes' clocks name actor 0 only)
+            s.append(("put", a, 1 << 20, 0, 1, 1 << 20, 0, {}, 7))
+            oo.append(MapUp(Dot(a, 1 << 20), 0, MapUp(Dot(1, 1 << 20), 0, MVRegPut(VClock({}), 7))))
+    st, slots, _ = nested_states(maps, K, K2, A, Dcap=Dcap)
+    ops = cg.map.encode_nested_ops(streams, A, "cuda:0")
+    status = cg.map.nested_apply_batch(st, *slots, ops, ctx=gpu_ctx).cpu().numpy()
+    assert (status == 0).all(), status
+    assert (slots[2].cpu().numpy() == 0).all()
+    assert not to_host(slots[0]).any() and not to_host(slots[1]).any()
+    for n in range(N):
+        exp = maps[n].copy()
+        for op in oops[n]:
+            exp.apply(op)
+        assert not exp.deferred
+        assert canon(decode_states(st, n, [])) == canon(exp), n

@@ -192,17 +192,9 @@ def test_map_orswot_apply_offsets_past_the_pools(gpu_ctx):
                                   ops._replace(vcounter=ops.vcounter.to(torch.int32)), ctx=gpu_ctx)
 
 
-def test_map_orswot_apply_long_deferred_list(gpu_ctx):
-    """More Map-level deferred removes than the 16 slots the kernel holds in LDS (round 6: the rest of
-    Dcap used in place in the caller's slot arrays): Map Rms from the far future on actor 0 (Ups on
-    actors 1..), 20+ removes per state at Dcap = 48, equal to the oracle's Map.apply."""
-    N, K, M, A, T, Dcap = 10, 4, 6, 5, 60, 48
-    maps = O.map_orswot_objects(N, K, M, A, seed=63, steps=120, p_vrm=0.3)
-    exps = [O.map_fold_objects([m]) for m in maps]
-    if any(len(e.val.deferred) > cg.map.VD_CAP for x in exps for e in x.entries.values()):
-        pytest.skip("nested deferred past the kernel's capacity")
-    res, kw, off = _states(gpu_ctx, maps, K, M, A)
-    rng = np.random.default_rng(17)
+def _future_rm_streams(rng, exps, K, M, A, T):
+    """Streams whose Map Rms carry clocks far ahead on actor 0 (distinct per op) while the Ups use
+    actors 1.. only: no Rm is ever dominated, so every one stays deferred (a long deferred list)."""
     streams, oops = [], []
     for x in exps:
         clk = {a: x.clock.get(a) for a in range(A)}
@@ -224,6 +216,24 @@ def test_map_orswot_apply_long_deferred_list(gpu_ctx):
                 oo.append(O.MapUp(O.Dot(a, c), k, O.OrswotAdd(O.Dot(va, vc), ms)))
         streams.append(ops)
         oops.append(oo)
+    return streams, oops
+
+
+@pytest.mark.parametrize("A", [5, 70, 512])
+def test_map_orswot_apply_long_deferred_list(gpu_ctx, A):
+    """More Map-level deferred removes than the 16 slots the kernel holds in LDS (round 6: the rest of
+    Dcap used in place in the caller's slot arrays): Map Rms from the far future on actor 0 (Ups on
+    actors 1..), 20+ removes per state at Dcap = 48, equal to the oracle's Map.apply.  A = 70 runs the
+    two-words-per-lane instances (lanes past A masked); at A = 512 fewer than 16 slots fit the wave's
+    LDS in either pass, so the slots past them are used in place."""
+    N, K, M, T, Dcap = 10, 4, 6, 60, 48
+    maps = O.map_orswot_objects(N, K, M, A, seed=63, steps=120, p_vrm=0.3)
+    exps = [O.map_fold_objects([m]) for m in maps]
+    # (the generated states keep their nested lists within the kernel's slots: a generator that stops
+    # doing so must fail here, not drop the cases that cover the in-place slots)
+    assert all(len(e.val.deferred) <= cg.map.VD_CAP for x in exps for e in x.entries.values())
+    res, kw, off = _states(gpu_ctx, maps, K, M, A)
+    streams, oops = _future_rm_streams(np.random.default_rng(17), exps, K, M, A, T)
     for n in range(N):
         for op in oops[n]:
             exps[n].apply(op)
@@ -254,3 +264,36 @@ def test_map_orswot_apply_long_deferred_list(gpu_ctx):
         assert got.clock == exps[n].clock and got.entries == exps[n].entries and got.deferred == exps[n].deferred, n
         longest = max(longest, len(exps[n].deferred))
     assert 20 <= longest <= Dcap
+
+
+def test_map_orswot_apply_vacated_slots_zeroed(gpu_ctx):
+    """A Map-level deferred list that grows past the 16 LDS slots and then empties (last Ups on actors 1
+    and 0 from past every remove's clock dominate them all): count 0, every slot written back zero,
+    state equal to the oracle's Map.apply."""
+    N, K, M, A, T, Dcap = 6, 6, 6, 5, 64, 48
+    maps = O.map_orswot_objects(N, K, M, A, seed=64, steps=0, p_vrm=0.0)
+    exps = [O.map_fold_objects([m]) for m in maps]
+    res, _, _ = _states(gpu_ctx, maps, K, M, A)
+    streams, oops = _future_rm_streams(np.random.default_rng(21), exps, K, M, A, T)
+    for s, oo in zip(streams, oops):
+        for a in (1, 0):  # (the removes' clocks name actor 0 only)
+            s.append(("add", a, 1 << 20, 0, 1, 1 << 20, [0]))
+            oo.append(O.MapUp(O.Dot(a, 1 << 20), 0, O.OrswotAdd(O.Dot(1, 1 << 20), [0])))
+    Kw = (K + 63) // 64
+    tdc, tdk = to_dev(np.zeros((N, Dcap, A), np.uint64)), to_dev(np.zeros((N, Dcap, Kw), np.uint64))
+    tcnt = torch.zeros(N, dtype=torch.int32, device="cuda:0")
+    ops = cg.map.encode_orswot_map_ops(streams, A, "cuda:0")
+    status = cg.map.orswot_apply_batch(res, tdc, tdk, tcnt, ops, ctx=gpu_ctx).cpu().numpy()
+    assert (status == 0).all(), status
+    assert (tcnt.cpu().numpy() == 0).all()
+    assert not to_host(tdc).any() and not to_host(tdk).any()
+    c, e, o, m = to_host(res.clock), to_host(res.ec), to_host(res.oc), to_host(res.ent)
+    vn, vc, vm = res.vd_n.cpu().numpy(), to_host(res.vd_clock), to_host(res.vd_mem)
+    for n in range(N):
+        for op in oops[n]:
+            exps[n].apply(op)
+        assert not exps[n].deferred
+        mw = (lambda k, i: vm[n, k, i]) if vm.ndim == 4 else (lambda k, i: vm[n, k, i:i + 1])  # noqa: E731
+        vd = {k: [(vc[n, k, i], O.bitmap_members(mw(k, i))) for i in range(int(vn[n, k]))] for k in range(K)}
+        got = O.dense_to_map_orswot(c[n], e[n], o[n], m[n], vd, [])
+        assert got.clock == exps[n].clock and got.entries == exps[n].entries and not got.deferred, n
